@@ -13,8 +13,13 @@ SURVEY.md 8d); configs[1]'s own 4096 bins are measured beside it (`extra.bins409
 Multi-GPU: bins are sharded, no data-path collective; one RCCL all-reduce of the episode
 totals after the timed region.  Default: "weak" scaling, 8192 bins per GPU; `--config cfg4|cfg5` are north_star's
 sharded configs (8192 k=10 bins / 16384 fine-heightmap bins divided over the GPUs: "strong").
-The timed region is repeated in blocks of --steps steps until it adds up to --min-seconds, so the figure does
-not depend on how few steps the caller asked for.
+The timed region is exactly --steps steps (--min-seconds S repeats that block until the blocks add up to S seconds).
+
+A plain run measures the headline figure only: set-up, prefill, warm-up, the timed steps, the result line.  --full adds
+what takes runs of its own or costs the timed region: the CPU baseline, the other configurations and sizes
+(`extra`), and HIP events around the kernels of the timed steps (`roofline.kernel_ms`).  --dump-outputs DIR writes
+what the last timed step computed as DIR/<name>.npy (float32 / float64; the inputs are seeded, so two builds can be
+compared output for output).
 
 Prints ONE JSON line on rank 0.
 """
@@ -252,13 +257,42 @@ def pmc_profile(workload):
     return prof.get("workloads", {}).get(workload), None
 
 
-def timed_run(env, a, dev, k, barrier, steps, prefill, warmup, min_seconds=0.0, agree=None):
+DUMP_BYTES = 48 << 20          # --dump-outputs writes at most this much in all (well inside 64 MB)
+
+
+def dump_outputs(path, env, obs, act, loc=None):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy in float32 / float64.  Per bin: the
+    step's info arrays (GroupedPackingEnv.step_info_host: reward, ratio, ep_reward, counter, ep_len, done, stable) and
+    the action the fused MINZ policy chose on the new observation (`next_action`); the observation rows themselves
+    (and, for k > 1, the candidate rows of the chosen buffer slot) of a fixed, seeded sample of the bins that fits the
+    budget, whose row indices are `obs_rows`."""
+    os.makedirs(path, exist_ok=True)
+    out = {name: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for name, v in env.step_info_host().items()}
+    out["next_action"] = torch.cat(act).cpu().numpy().astype(np.float32)
+    big = [("obs", torch.cat(obs))] + ([("loc_obs", torch.cat(loc))] if loc is not None else [])
+    n = big[0][1].shape[0]
+    row_bytes = sum(t.shape[1] * 4 for _, t in big) + 8
+    rows = min(n, (DUMP_BYTES - sum(v.nbytes + 4096 for v in out.values()) - 8192) // row_bytes)   # (+ .npy headers)
+    pick = np.sort(np.random.default_rng(0).choice(n, size=rows, replace=False))
+    out["obs_rows"] = pick.astype(np.float64)
+    idx = torch.from_numpy(pick).to(big[0][1].device)
+    for name, t in big:
+        out[name] = t.index_select(0, idx).cpu().numpy().astype(np.float32)
+    for name, v in out.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+    return sorted(out)
+
+
+def timed_run(env, a, dev, k, barrier, steps, prefill, warmup, min_seconds=0.0, agree=None, kernel_timing=True,
+              on_finish=None):
     """prefill (untimed: every bin deep in its own episode, terminal steps and auto-resets in the mix),
     warm-up, then blocks of exactly `steps` timed steps, each between two barriers, until the timed blocks add up to
     `min_seconds` (at least one block; `agree` makes the ranks agree on "enough").  `env` is a GroupedPackingEnv: every
     group of bins is stepped on its own stream, policy kernel then transition, without waiting for the other groups
-    (one group = one launch per kernel over all bins).  -> (seconds, timed steps, transition ms per placement summed
-    over the groups' own event pairs, episodes finished inside the timed blocks)."""
+    (one group = one launch per kernel over all bins).  `kernel_timing`: HIP events around the transitions of the timed
+    blocks (else the kernel figure is None); `on_finish(obs, actions, loc)`: called after the last timed step with the
+    per-group observation, next-action and (k > 1) candidate buffers.  -> (seconds, timed steps, transition ms per
+    placement summed over the groups' own event pairs, episodes finished inside the timed blocks)."""
     G, per = env.num_groups, env.per
     launches = 2 if k > 1 else 1               # transitions per placement
     obs = env.reset()
@@ -297,8 +331,9 @@ def timed_run(env, a, dev, k, barrier, steps, prefill, warmup, min_seconds=0.0, 
     done_before = float(env.episode_totals()[0].item())
     elapsed, timed_steps, kms = 0.0, 0, []
     while True:
-        for e in env.groups:                       # HIP events around every fourth transition, on its stream (an event
-            e.enable_kernel_timing((steps * launches + every - 1) // every, every)   # pair per step costs the stream ~5 %)
+        if kernel_timing:
+            for e in env.groups:                       # HIP events around every fourth transition, on its stream (an event
+                e.enable_kernel_timing((steps * launches + every - 1) // every, every)   # pair per step costs the stream ~5 %)
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -306,17 +341,21 @@ def timed_run(env, a, dev, k, barrier, steps, prefill, warmup, min_seconds=0.0, 
         barrier()
         elapsed += time.perf_counter() - t0
         timed_steps += steps
-        kms.append(float(sum(e.kernel_times_ms().mean() for e in env.groups)) * launches)
+        if kernel_timing:
+            kms.append(float(sum(e.kernel_times_ms().mean() for e in env.groups)) * launches)
         enough = elapsed >= min_seconds
         if agree is not None:
             enough = agree(enough)
         if enough:
             break
     env.check_device_error()
-    for e in env.groups:
-        e.enable_kernel_timing(0)
+    if kernel_timing:
+        for e in env.groups:
+            e.enable_kernel_timing(0)
+    if on_finish is not None:
+        on_finish(cur, act, loc if k > 1 else None)
     finished = float(env.episode_totals()[0].item()) - done_before
-    return elapsed, timed_steps, float(np.mean(kms)), finished
+    return elapsed, timed_steps, float(np.mean(kms)) if kms else None, finished
 
 
 # BASELINE.json configs as bench modes: (workload, global bins or None = --bins per GPU, default scaling)
@@ -401,10 +440,16 @@ def actor_loop_rate(bins, dev, steps=100, capacity=64):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200, help="steps per timed block")
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (one block; see --min-seconds)")
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--min-seconds", type=float, default=1.0,
-                    help="repeat the timed block of --steps steps until the timed blocks add up to this (0 = one block)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the timed block of --steps steps until the timed blocks add up to this (0 = one block: "
+                         "exactly --steps timed steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline, the extra configurations and sizes, "
+                         "and HIP events around the kernels of the timed steps (roofline.kernel_ms)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0's bins)")
     ap.add_argument("--prefill", type=int, default=300,
                     help="untimed steps before the warm-up that bring every bin to a steady-state episode mix")
     ap.add_argument("--bins", type=int, default=None, help="bins per GPU (weak scaling; default 8192 = north_star's target "
@@ -417,8 +462,9 @@ def main():
                     help="independent groups of bins, each stepped on its own stream (0 = as many as the library recommends "
                          "for the data and size: vec_env.groups_for, i.e. two or one)")
     ap.add_argument("--tuning", type=int, default=0, help="irbpp_config::tuning bit flags (A/B measurements; results never change)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra measurements (other configs, 8192 bins, grouped, VecEnv)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="under --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="under --full: skip the extra measurements (other configs, 8192 bins, "
+                    "grouped, VecEnv)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend; nccl is RCCL on ROCm "
                     "(gloo + several ranks on one device is only for dry runs of the multi-rank path)")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
@@ -446,7 +492,7 @@ def main():
 
     from irbpp_amd import distributed as D
     cpu = None
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(workload, a.cpu_budget)         # before HIP is initialised: the pool forks
     if world != a.gpus:
         raise SystemExit(f"bench.py --gpus {a.gpus} is running as {world} rank(s): launch one rank per GPU "
@@ -481,8 +527,15 @@ def main():
     def agree(flag):                   # every rank stops after the same block
         return D.max_over_ranks(0.0 if flag else 1.0, dev) == 0.0
 
+    dumped = None
+
+    def dump(obs, act, loc):
+        nonlocal dumped
+        if a.dump_outputs and rank == 0:
+            dumped = dump_outputs(a.dump_outputs, env, obs, act, loc)
+
     my_elapsed, timed_steps, kernel_ms, finished = timed_run(env, a, dev, k, barrier, a.steps, a.prefill, a.warmup,
-                                                             a.min_seconds, agree)
+                                                             a.min_seconds, agree, kernel_timing=a.full, on_finish=dump)
     lds_bytes, kernel_name = env.groups[0].kernel_info()
     from irbpp_amd.vec_env import group_stream_report
     probe = group_stream_report(dev)           # what the stream probe behind groups_for saw in this process
@@ -514,7 +567,7 @@ def main():
     # north_star's 8192 bins on one GPU, the other BASELINE configs at their per-GPU sizes, and the rate a user of the
     # reference-facing VecEnv API gets.
     extra, grouped = None, None
-    if world == 1 and not a.no_extra:
+    if a.full and world == 1 and not a.no_extra:
         extra = {}
         if groups != 1:
             extra["one_group"] = side_run(workload, bins, 1)             # the same bins as one launch per kernel
@@ -590,6 +643,9 @@ def main():
             out["extra"] = extra
         if cpu is not None:
             out["cpu_baseline"] = cpu
+        out["full"] = a.full
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
     if dist.is_initialized():
         dist.destroy_process_group()
     if rank == 0:

@@ -100,3 +100,34 @@ def test_pmc_profile_is_quoted_only_for_matching_kernel_sources(tmp_path, monkey
     doc["kernel_source_sha"] = source_hash()
     (tmp_path / "profiles" / "pmc_hbm.json").write_text(json.dumps(doc))
     assert bench.pmc_profile("blockout") == ({"bins": 16384, "hbm_bytes_per_launch": 1.0}, None)
+
+
+def test_dump_outputs_is_a_fixed_sample_inside_the_budget(tmp_path):
+    """--dump-outputs: float32 / float64 arrays only, at most bench.DUMP_BYTES in all, the observation rows a seeded sample
+    (the same rows every time) whose indices are written beside them."""
+    import torch
+
+    class Info:                                       # stands in for GroupedPackingEnv.step_info_host
+        def step_info_host(self):
+            n = 8192
+            return dict(reward=np.linspace(0, 1, n), counter=np.arange(n, dtype=np.int32), done=np.arange(n) % 7 == 0)
+
+    gen = torch.Generator().manual_seed(0)
+    obs = [torch.rand((4096, 3533), generator=gen) for _ in range(2)]
+    act = [torch.arange(4096, dtype=torch.int32) for _ in range(2)]
+    names = bench.dump_outputs(str(tmp_path / "a"), Info(), obs, act)
+    assert set(names) == {"reward", "counter", "done", "next_action", "obs", "obs_rows"}
+    total = sum(os.path.getsize(tmp_path / "a" / (n + ".npy")) for n in names)
+    assert total <= bench.DUMP_BYTES <= 64e6
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    rows = got["obs_rows"].astype(np.int64)
+    assert 0 < len(rows) < 8192 and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(got["obs"], torch.cat(obs).numpy()[rows])
+    np.testing.assert_array_equal(got["next_action"], np.tile(np.arange(4096), 2).astype(np.float32))
+    assert got["reward"].dtype == np.float64 and got["done"].sum() == (np.arange(8192) % 7 == 0).sum()
+    bench.dump_outputs(str(tmp_path / "b"), Info(), obs, act, loc=obs)        # k > 1: candidate rows share the budget
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "obs.npy"), np.load(tmp_path / "b" / "loc_obs.npy"))
+    assert sum(os.path.getsize(p) for p in (tmp_path / "b").iterdir()) <= bench.DUMP_BYTES
+    again = bench.dump_outputs(str(tmp_path / "c"), Info(), obs, act)
+    assert again == names and np.array_equal(np.load(tmp_path / "c" / "obs_rows.npy"), got["obs_rows"])

@@ -914,6 +914,54 @@ def test_bench_gpus2_spawns_two_real_ranks():
     one.close()
 
 
+def test_bench_plain_run_times_exactly_steps_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` times exactly --steps steps and measures nothing beside the headline (no CPU baseline, no extras,
+    no kernel events); --dump-outputs writes what the last timed step handed its caller, the same in two runs and the same
+    as a plain GpuPackingEnv stepped as many times."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for var in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(var, None)
+    prefill, warmup, steps, bins = 40, 3, 7, 256
+
+    def run(out):
+        res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--bins", str(bins),
+                              "--prefill", str(prefill), "--warmup", str(warmup), "--steps", str(steps),
+                              "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, env=env)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, res.stdout[-2000:]
+        return json.loads(lines[0])
+
+    lines = [run(tmp_path / "a"), run(tmp_path / "b")]
+    for line in lines:
+        assert line["steps"] == line["steps_timed_total"] == steps and line["timed_blocks"] == 1 and line["full"] is False
+        assert "cpu_baseline" not in line and "extra" not in line and line["roofline"]["kernel_ms"] is None
+        assert abs(line["value"] - bins / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    names = lines[0]["dumped_outputs"]["arrays"]
+    assert {"obs", "obs_rows", "reward", "done", "next_action"} <= set(names)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    for n in names:
+        assert got[n].dtype in (np.float32, np.float64)
+        np.testing.assert_array_equal(got[n], np.load(tmp_path / "b" / (n + ".npy")))
+    np.testing.assert_array_equal(got["obs_rows"], np.arange(bins))          # few bins: every row fits the budget
+
+    sh, seqs, kw = __import__("bench").make_workload("blockout")
+    one = GpuPackingEnv(sh, seqs, bins, device=DEV, **kw)
+    obs = one.reset()
+    for _ in range(prefill + warmup + steps):
+        obs, rew, done = one.step(one.policy_minz(obs))
+    np.testing.assert_array_equal(got["obs"], obs.cpu().numpy())
+    np.testing.assert_array_equal(got["reward"], rew.cpu().numpy())
+    np.testing.assert_array_equal(got["done"], done.cpu().numpy().astype(np.float32))
+    np.testing.assert_array_equal(got["next_action"], one.policy_minz(obs).cpu().numpy().astype(np.float32))
+    one.check_device_error()
+    one.close()
+
+
 @pytest.mark.parametrize("mode", [1, 2])
 def test_stability_proxy_matches_its_specification(mode):
     """irbpp_config::stability -- the static support test that stands in for the rigid-body settling the path
