@@ -19,12 +19,15 @@
  *     handed over with irbpp_register_obs_buffer is kept complete by the library instead
  *     (same contents, fewer stores).
  *
- * Limits (irbpp_create returns IRBPP_ERR_ARG beyond them): action grid <= 32 x 32 cells (up to 16 x 16: the tuned pipeline;
- * 17 .. 32 a side, e.g. resolutionA = 0.01: the capacity path of csrc/irbpp_wide.hip, one kernel per observation, heightmap
- * <= 64 x 64 cells, no stability proxy, no stage-level tooling entry points), heightmap <= 128 x 128 cells with resolutionA an
- * integer multiple of resolutionH and the bin an integer number of action cells; n_rot <= 8; selected <= 1024; buffer_size <= 16;
- * bin[2] / resolution_z <= 31 height levels (cvTools.py:78 codes a level in 6 bits: level + 32);
- * num_bins <= 1048576 per device.  Item ids are < 65536 in the placement log.
+ * Limits (irbpp_create returns IRBPP_ERR_ARG beyond them): action grid <= 32 x 32 cells, heightmap <= 128 x 128 cells with
+ * resolutionA an integer multiple of resolutionH and the bin an integer number of action cells; n_rot <= 8; selected <= 1024;
+ * buffer_size <= 16; floor(bin[2] / resolution_z) <= 222 height levels (cvTools.py:78; a level is coded as level + 32 in a byte,
+ * 255 meaning none); num_bins <= 1048576 per device.  Item ids are < 65536 in the placement log.
+ * Two regimes: up to 16 x 16 action cells AND up to 31 height levels (every README command of the reference) run the tuned
+ * pipeline.  17 .. 32 cells a side (resolutionA = 0.01), or 32 .. 222 height levels at any grid size (resolution_z = 0.005 on the
+ * 0.30 m bin: 60; a 0.60 m bin at 0.01: 60), run the capacity path of csrc/irbpp_wide.hip, one kernel per observation, with the
+ * same results and its own limits: heightmap <= 64 x 64 cells, no stability proxy (stability must be 0), and the stage-level
+ * tooling entry points irbpp_possible_position, irbpp_heuristic_action and irbpp_convex_hull_actions answer IRBPP_ERR_ARG.
  */
 #ifndef IRBPP_H
 #define IRBPP_H
@@ -404,7 +407,7 @@ int irbpp_debug_kernel_times(irbpp_env* env, float* ms_host, int32_t max_count, 
 /* Device-side error word raised by kernels (0 = none).  Synchronises the stream. */
 int irbpp_device_error(irbpp_env* env, void* stream, int32_t* flags_out);
 
-#define IRBPP_DEVERR_LEVEL_RANGE   1   /* a height level fell outside the 64 supported bins  */
+#define IRBPP_DEVERR_LEVEL_RANGE   1   /* a height level fell outside the level codes of the configuration */
 #define IRBPP_DEVERR_TRACE_GUARD   2   /* border following exceeded its iteration guard      */
 #define IRBPP_DEVERR_BAD_ITEM      4   /* item id outside the loaded shape table             */
 #define IRBPP_DEVERR_BAD_BIN       8   /* irbpp_reset_bins: bin index outside [0, num_bins)  */

@@ -200,15 +200,19 @@ int irbpp_create(const irbpp_config* cfg, irbpp_env** out) {
     P.Hc = P.Hx * P.Hy;
     P.AC = P.Ax * P.Ay;
     if (P.Ax > 32 || P.Ay > 32 || P.Ax < 1 || P.Ay < 1 || P.Hc > 128 * 128) { delete env; return IRBPP_ERR_ARG; }
-    // 17 .. 32 action cells a side (resolutionA = 0.01): the capacity path of irbpp_wide.hip -- one kernel per observation, every
-    // stage in the bin's workgroup; no stability proxy, no item streams' extras are affected, the stage-level tooling entry points
-    // (possible_position, heuristic_action, convex_hull_actions) answer IRBPP_ERR_ARG
-    P.wide = (P.Ax > 16 || P.Ay > 16) ? 1 : 0;
+    // height levels (cvTools.py:78): a placement height never exceeds bin_z, so floor(bin_z / resolution_z) levels cover it.  The
+    // tuned pipeline codes them in 6 bits (level + 32), the capacity path in 8 (TUNED_MAX_LEVELS, MAX_LEVELS)
+    const double levels = floor(cfg->bin[2] / cfg->resolution_z + 1e-9);
+    if (!(levels <= (double)MAX_LEVELS)) { delete env; return IRBPP_ERR_ARG; }
+    const bool deep = levels > (double)TUNED_MAX_LEVELS;
+    // 17 .. 32 action cells a side (resolutionA = 0.01), or more than 31 height levels (resolutionZ = 0.005 on the 0.30 m bin): the
+    // capacity path of irbpp_wide.hip -- one kernel per observation, every stage in the bin's workgroup; no stability proxy, no item
+    // streams' extras are affected, the stage-level tooling entry points (possible_position, heuristic_action, convex_hull_actions)
+    // answer IRBPP_ERR_ARG
+    P.wide = (P.Ax > 16 || P.Ay > 16 || deep) ? 1 : 0;
     P.vrow = P.wide ? WIDE_VROW : 16;
     if (P.wide && (P.Hc > 64 * 64 || cfg->stability != 0)) { delete env; return IRBPP_ERR_ARG; }
     if (P.Hx != P.Ax * P.step || P.Hy != P.Ay * P.step) { delete env; return IRBPP_ERR_ARG; }   // phase-plane tile layout
-    // height levels are coded in 6 bits (level + 32): a placement height never exceeds bin_z, so 31 levels must cover it
-    if (floor(cfg->bin[2] / cfg->resolution_z + 1e-9) > 31.0) { delete env; return IRBPP_ERR_ARG; }
     P.traj_start = cfg->traj_start;
     P.goff = cfg->global_offset;
     P.gbins = cfg->global_bins > 0 ? cfg->global_bins : cfg->num_bins;
@@ -220,7 +224,7 @@ int irbpp_create(const irbpp_config* cfg, irbpp_env** out) {
     P.split = 1;                                            // transition -> trace -> emit kernels
     P.stability = cfg->stability < 0 ? 0 : (cfg->stability > 2 ? 2 : cfg->stability);
     P.rect = (cfg->tuning & IRBPP_TUNE_RECT) ? 1 : 0;
-    P.wimg = P.R * 64;
+    P.wimg = P.R * (deep ? (((int)levels + 33 + 31) & ~31) : 64);   // level + 32 for levels up to `levels`, in whole words of 32 codes
     P.seg_cap = P.wide ? 64 : 2 * ((P.N + NXCD - 1) / NXCD) * P.R * P.AC;      // (the wide path hands nothing over between kernels)
     P.round_cap = P.wide ? 16 : (P.N / NXCD + 64) * 16;
     layout_lds_host(P);                 // redone by irbpp_load_shapes if the block path applies
@@ -1150,9 +1154,14 @@ int irbpp_debug_kernel_info(const irbpp_env* env, int32_t* lds_bytes, const char
              pick_env_kernel(env).name, cpw > 64 ? "_refill" : cpw == 64 ? "" : (cpw == 32 ? "_c32" : "_c16"), emit,
              !split_apply(env, n) ? "" : (env->P.K > 1 ? (n < 2048 ? " (step: irbpp_apply_wg_kernel alone)" : " (step: irbpp_apply_kernel alone)")
                                                        : " (step: irbpp_apply_kernel in front, transition kernel in MODE_OBSERVE)"));
-    if (env->P.wide)
-        snprintf(const_cast<irbpp_env*>(env)->kernel_names, sizeof env->kernel_names, "irbpp_wide_kernel alone (action grid of %d x %d cells)%s", env->P.Ax, env->P.Ay,
-                 env->P.K > 1 ? " (step: the apply kernel alone)" : " (step: irbpp_apply_kernel in front)");
+    if (env->P.wide) {
+        // (what sends the configuration there: the grid, and / or more height levels than the tuned pipeline codes)
+        const int levels = (int)floor(env->P.bin_z / env->P.res_z + 1e-9);
+        char why[48] = "";
+        if (levels > TUNED_MAX_LEVELS) snprintf(why, sizeof why, ", %d height levels", levels);
+        snprintf(const_cast<irbpp_env*>(env)->kernel_names, sizeof env->kernel_names, "irbpp_wide_kernel alone (action grid of %d x %d cells%s)%s", env->P.Ax,
+                 env->P.Ay, why, env->P.K > 1 ? " (step: the apply kernel alone)" : " (step: irbpp_apply_kernel in front)");
+    }
     else if (chain_launch(env, n)) {
         const bool s1 = spec == 1;
         snprintf(const_cast<irbpp_env*>(env)->kernel_names, sizeof env->kernel_names, "%s alone (observation finished in the bin's workgroup)%s",

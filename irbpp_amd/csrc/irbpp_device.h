@@ -35,6 +35,11 @@ constexpr int XCD_STRIDE = 64;                     // ints between the lists' co
 constexpr int ROUND_POINTS = 64 * IRBPP_TRACE_P, ROUND_BYTES = ROUND_POINTS * 7;   // a round record of the polygon kernel: [points | border length | border
                                                                      // start] per position, then the vertex-row index of the position's border
 constexpr int MAX_BINS = 1 << 20;                 // bins per device (irbpp_create refuses more): keeps every per-launch index an int32
+// Height levels: floor(bin_z / resolution_z), the highest level a placement can reach (cvTools.py:78).  The tuned pipeline codes a
+// level in 6 bits (level + 32, a uint64 of present levels per rotation); configurations with more levels take the capacity path
+// (irbpp_wide.hip), whose uint8 codes reserve 255 for "no level": level + 32 <= 254.  irbpp_create refuses more.
+constexpr int TUNED_MAX_LEVELS = 31;
+constexpr int MAX_LEVELS = 222;
 
 struct ShapeRot {
     int32_t fx, fy;        // footprint in heightmap cells: ceil(round(extents,6)/resH)  (space.py:105)
@@ -162,13 +167,15 @@ struct Params {
     // 16 whole contour stage.
     int32_t dbg_repeat;
     int32_t split;         // 1: transition kernel -> trace kernel -> emit kernel; 0: everything in the transition kernel
-    int32_t wimg;          // level images a bin can hand over: R * 64
+    int32_t wimg;          // level images a bin can have: R * level codes (level + 32) -- R * 64 up to TUNED_MAX_LEVELS; beyond (the
+                           // capacity path's tables) levels + 33 codes rounded up to 32
     int32_t seg_cap;       // entries of one XCD's flat candidate list: twice the worst case (R*AC per bin) of its share of the bins
     int32_t round_cap;     // round records of one XCD's list (a full list makes the trace kernel approximate in place)
     int32_t heavy_cap, heavy_thr;   // bins the emit kernel can serve first (0: off); border starts + isolated pixels that make a bin one of them
     int32_t stability;     // 0 off, 1 rate accepted placements, 2 refuse unstable ones (irbpp_config::stability)
-    int32_t wide;          // action grid of 17 .. 32 cells a side: the capacity path of irbpp_wide.hip (one kernel per observation)
-    int32_t vrow;          // words per rotation of w_valid (naiveMask bit rows): 16, or 32 on a wide grid
+    int32_t wide;          // action grid of 17 .. 32 cells a side, or more than 31 height levels: the capacity path of irbpp_wide.hip
+                           // (one kernel per observation)
+    int32_t vrow;          // words per rotation of w_valid (naiveMask bit rows): 16, or 32 on the capacity path
     int32_t rect;          // IRBPP_TUNE_RECT: isolated solid rectangles are answered by the transition kernel instead of the trace kernel (A/B)
 };
 

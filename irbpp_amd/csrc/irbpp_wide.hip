@@ -1,5 +1,6 @@
 // irbpp_wide.hip -- WIDE action grids: 17 .. 32 cells a side (resolutionA = 0.01 on the 0.32 m bin: space.py:19-24 takes any
-// resolutionA with an integral stepSize; every README command of the reference uses 0.02 = 16 x 16).
+// resolutionA with an integral stepSize; every README command of the reference uses 0.02 = 16 x 16), and any grid with more than
+// TUNED_MAX_LEVELS height levels (resolutionZ = 0.005 on the 0.30 m bin: 60; a 0.60 m bin at 0.01: 60) -- up to MAX_LEVELS.
 //
 // The step's tuned kernels hold a contour point in ONE byte (x | y << 4), a level image in sixteen 16-bit row words and an
 // action cell per thread: all of that is the 16 x 16 grid's.  This file is the CAPACITY path for larger grids -- correct first,
@@ -7,7 +8,8 @@
 //
 //   [irbpp_apply_kernel in front for a step: it is geometry-free]
 //   irbpp_wide_kernel: reset / get_action_candidates / observe bookkeeping (env_transition's), overlap test over the footprint's
-//   cell lists (space.py:98-129), level codes (cvTools.py:78-79), one level image after the other as 32 rows of 32 bits,
+//   cell lists (space.py:98-129), level codes (cvTools.py:78-79: level + 32 in a byte, P.wimg / R of them per rotation), one level
+//   image after the other as 32 rows of 32 bits,
 //   candidate starts, the plain border walk and approxPolyDP + convexity lane-serially (contours_device.h:
 //   trace_border_wide, approx_and_convex_t<uint16_t, 5>: host-tested against the oracle), candidate rows in np.unique order,
 //   the > S selection / the no-candidate fallback by a radix select over keys in LDS, rows, candidate keys, fused MINZ policy.
@@ -43,7 +45,7 @@ __host__ __device__ inline WideLayout wide_layout(const Params& P) {
     WideLayout w{};
     int off = 0;
     w.o_sr = off;       off += align16(P.R * (int)sizeof(ShapeRot));
-    w.o_present = off;  off += align16(P.R * 8);
+    w.o_present = off;  off += align16(P.wimg / 8);                            // (wimg = R * level codes: R * 64 up to 31 levels)
     w.o_vmask = off;    off += align16(P.R * WIDE_VROW * 4);
     w.o_vbits = off;    off += align16(P.R * WIDE_VROW * 4);
     w.o_red = off;      off += 512;
@@ -56,8 +58,8 @@ __host__ __device__ inline WideLayout wide_layout(const Params& P) {
     int k2 = k0;
     w.o_rows = k2;      k2 += 2 * WIDE_IB * 32 * 4;
     w.o_clist = k2;     k2 += WIDE_CLIST * 2;
-    w.o_lut = k2;       k2 += align16(P.R * 64 * 2);
-    w.o_imglist = k2;   k2 += align16(P.R * 64 * 2);
+    w.o_lut = k2;       k2 += align16(P.wimg * 2);
+    w.o_imglist = k2;   k2 += align16(P.wimg * 2);
     const int k3 = k0 + align16((P.R * P.AC + P.S) * 4 + 64);
     off = k2 > k3 ? k2 : k3;
     // region T
@@ -185,7 +187,7 @@ irbpp_wide_kernel(const Params P, const Tables T, const State S, const StepIO io
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const WideLayout W = wide_layout(P);
     int* const srw = (int*)(smem + W.o_sr);
-    uint32_t* const present = (uint32_t*)(smem + W.o_present);        // [R][2]: bit `code` of rotation r
+    uint32_t* const present = (uint32_t*)(smem + W.o_present);        // [R][LC / 32]: bit `code` of rotation r
     uint32_t* const vmask = (uint32_t*)(smem + W.o_vmask);            // [R][32] vertex bits: word row, bit col
     uint32_t* const vbits = (uint32_t*)(smem + W.o_vbits);            // [R][32] naiveMask bit rows
     double* const redd = (double*)(smem + W.o_red);
@@ -204,6 +206,8 @@ irbpp_wide_kernel(const Params P, const Tables T, const State S, const StepIO io
     const int tid = threadIdx.x, lane = tid & 63;
     const int R = P.R, AC = P.AC, Ax = P.Ax, Ay = P.Ay;
     constexpr int VR = WIDE_VROW;
+    const int LC = P.wimg / R, PW = LC >> 5;                         // level codes per rotation, their words in `present`
+    const int top_code = LC - 1 < 254 ? LC - 1 : 254;                // (255: no level)
 
     const bool some = mode == MODE_RESET && io.bin_list != nullptr;
     const int slot = (int)blockIdx.x + io.block_off;
@@ -265,7 +269,7 @@ irbpp_wide_kernel(const Params P, const Tables T, const State S, const StepIO io
     // ---- Space.get_possible_position (space.py:98-129) over the footprint's masked-in bottom cells
     constexpr int SRW = sizeof(ShapeRot) / 4;
     if (item >= 0) for (int t = tid; t < R * SRW; t += BLOCK) srw[t] = ((const int*)(T.sr + (size_t)item * R))[t];
-    for (int i = tid; i < R * 2; i += BLOCK) present[i] = 0u;
+    for (int i = tid; i < R * PW; i += BLOCK) present[i] = 0u;
     for (int i = tid; i < R * VR; i += BLOCK) { vmask[i] = 0u; vbits[i] = 0u; }
     for (int i = tid; i < R * AC; i += BLOCK) lev[i] = 255;
     __syncthreads();
@@ -324,10 +328,10 @@ irbpp_wide_kernel(const Params P, const Tables T, const State S, const StepIO io
                 zdst[r * AC + c] = m;
                 if (li != -1) {                                            // level -1 is skipped (cvTools.py:84)
                     const int idx = li + 32;
-                    if (idx < 0 || idx > 63) raise_error(S, IRBPP_DEVERR_LEVEL_RANGE);
+                    if (idx < 0 || idx > top_code) raise_error(S, IRBPP_DEVERR_LEVEL_RANGE);
                     else {
                         lev[r * AC + c] = (uint8_t)idx;
-                        atomicOr(&present[r * 2 + (idx >> 5)], 1u << (idx & 31));
+                        atomicOr(&present[r * PW + (idx >> 5)], 1u << (idx & 31));
                     }
                 }
                 atomicOr(&vbits[r * VR + X], 1u << Y);
@@ -356,16 +360,16 @@ irbpp_wide_kernel(const Params P, const Tables T, const State S, const StepIO io
     uint32_t* const tstk = (uint32_t*)(tdst + WIDE_LCAP);
     uint8_t* const big = S.w_big + (size_t)b * wide_scratch_bytes(P);
     unsigned long long* const skl = (unsigned long long*)big;       // (the > S selection's sortable values: the same global scratch, later)
-    for (int i = tid; i < R * 64; i += BLOCK) lut[i] = 0xFFFF;
+    for (int i = tid; i < R * LC; i += BLOCK) lut[i] = 0xFFFF;
     __syncthreads();
     if (tid == 0) {                                  // images in (rotation, level) order
         int ni = 0;
         for (int r = 0; r < R; ++r)
-            for (int half = 0; half < 2; ++half)
-                for (uint32_t pm = present[r * 2 + half]; pm != 0u; pm &= pm - 1u) {
-                    const int code = half * 32 + __ffs((int)pm) - 1;
+            for (int word = 0; word < PW; ++word)
+                for (uint32_t pm = present[r * PW + word]; pm != 0u; pm &= pm - 1u) {
+                    const int code = word * 32 + __ffs((int)pm) - 1;
                     imglist[ni] = (uint16_t)((r << 8) | code);
-                    lut[r * 64 + code] = (uint16_t)ni;
+                    lut[r * LC + code] = (uint16_t)ni;
                     ++ni;
                 }
         cnt[2] = ni;
@@ -382,7 +386,7 @@ irbpp_wide_kernel(const Params P, const Tables T, const State S, const StepIO io
             for (int c = tid; c < AC; c += BLOCK) {
                 const int code = lev[r * AC + c];
                 if (code != 255) {
-                    const int slot = (int)lut[r * 64 + code] - base;
+                    const int slot = (int)lut[r * LC + code] - base;
                     if (slot >= 0 && slot < nbi) {
                         const int X = fdiv(c, Ay, P.mg_ay), Y = c - X * Ay;
                         atomicOr(&rows[slot * 32 + X], 1u << Y);
