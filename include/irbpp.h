@@ -311,6 +311,44 @@ int irbpp_set_heightmaps(irbpp_env* env, const double* hm_dev, void* stream);
  * The multi-GPU runner all-reduces these four numbers (RCCL). */
 int irbpp_episode_totals(irbpp_env* env, double* out_dev, void* stream);
 
+/* The trainer's logged episode metrics on the device (trainer.py:145-147 deque(maxlen=10) x 3, :168-178 append on done,
+ * :215-222 add_scalar of their mean / max / min): a window of the last `window` finished episodes, in the order (step they
+ * finished in, global bin), kept per environment and snapshotted after every step, so that the rows the trainer would have
+ * logged can be computed for hundreds of steps at once without a host round trip per step.
+ * An entry: r = round(ep_reward, 6) with Python's round (monitor.py:64), ratio and counter of the step outputs. */
+typedef struct {
+    int64_t key;              /* finish step << 32 | global bin (global_offset + b): the window's order            */
+    double  r;                /* Monitor 'r': Python's round(ep_reward, 6)                                         */
+    double  ratio;            /* info['ratio']                                                                      */
+    int32_t counter;          /* info['counter']                                                                    */
+    int32_t reserved;
+} irbpp_episode_entry;
+/* Caller-owned device buffers of one window (all zeroed before the first attach: a zeroed window is empty at step 0).
+ * Steps are counted from 1 (trainer.py:158) since the buffers were zeroed; step T's window is snapshot row T % history. */
+typedef struct {
+    irbpp_episode_entry* ring_dev;      /* [window]: the live window, a ring                                        */
+    irbpp_episode_entry* snapshot_dev;  /* [history][window]: the window after each step, oldest entry first         */
+    int32_t* rows_dev;                  /* [history][2]: step held by the snapshot row, entries in it                */
+    int32_t* state_dev;                 /* [4]: steps recorded, entries in the window, ring head, unused             */
+    int32_t window;                     /* W, 1..1024 (the reference: 10)                                            */
+    int32_t history;                    /* H >= 1 snapshot rows: read at least every H steps                         */
+} irbpp_episode_window;
+/* Attaches a window to the environment (NULL detaches): from then on every irbpp_step -- both overlap paths, online and
+ * buffered -- launches one small update kernel on its stream after the step's kernels, which appends the bins finished by
+ * the step (done_dev) to the window and writes the snapshot.  While attached, a step whose irbpp_step_out lacks done_dev,
+ * ep_reward_dev, ratio_dev or counter_dev is IRBPP_ERR_ARG.  Works with IRBPP_TUNE_GRAPH (the launch follows the replayed
+ * graph).  Detached, a step launches exactly what it launched before.  The buffers must outlive the attachment. */
+int irbpp_set_episode_window(irbpp_env* env, const irbpp_episode_window* window);
+/* The rows the trainer logs (trainer.py:215-222) for steps first_step .. first_step + n_steps - 1 of n_parts windows whose
+ * bins together are the trainer's envs (groups of bins, ranks: any order; the global bin index orders them).  out_dev:
+ * float64[n_steps][7] = (T, n, mean r, max r, min r, mean ratio, mean counter), n = len(deque) and the five statistics NaN
+ * when n == 0 (the trainer logs nothing then); every mean equals np.mean over the deque bit for bit.  A step that some part
+ * has not recorded yet has n = -2, a step whose snapshot row was overwritten (more than `history` steps ago) n = -1, both
+ * with NaN statistics.  All parts need the same window and history; n_parts 1..64, n_steps 1..history, first_step >= 1.
+ * Asynchronous on `stream`, which must follow the steps of every part. */
+int irbpp_episode_metrics(const irbpp_episode_window* parts, int32_t n_parts, int32_t first_step, int32_t n_steps,
+                          double* out_dev, void* stream);
+
 /* replaces: PackingGame.packed (binPhy.py:141,296), the per-episode placement record that
  * tools.test saves to trajs.npy (tools.py:339-340).  While set, every successful placement of
  * bin b, the i-th of its episode (i < capacity), stores meta_dev[b*capacity+i] =

@@ -42,6 +42,11 @@ class IrbppReplayStore(C.Structure):
                 ("n_env", C.c_int32), ("capacity", C.c_int32), ("obs_len", C.c_int32)]
 
 
+class IrbppEpisodeWindow(C.Structure):
+    _fields_ = [("ring_dev", C.c_void_p), ("snapshot_dev", C.c_void_p), ("rows_dev", C.c_void_p), ("state_dev", C.c_void_p),
+                ("window", C.c_int32), ("history", C.c_int32)]
+
+
 class IrbppStepOut(C.Structure):
     _fields_ = [("reward_dev", C.c_void_p), ("done_dev", C.c_void_p), ("counter_dev", C.c_void_p),
                 ("ratio_dev", C.c_void_p), ("ep_reward_dev", C.c_void_p), ("ep_len_dev", C.c_void_p),
@@ -84,6 +89,8 @@ SIGNATURES = {
     "irbpp_set_heightmaps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "irbpp_episode_totals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "irbpp_set_placement_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "irbpp_set_episode_window": (C.c_int, [C.c_void_p, C.POINTER(IrbppEpisodeWindow)]),
+    "irbpp_episode_metrics": (C.c_int, [C.POINTER(IrbppEpisodeWindow), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "irbpp_sumtree_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "irbpp_sumtree_find": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,

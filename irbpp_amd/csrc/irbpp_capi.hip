@@ -19,6 +19,7 @@
 #include "irbpp_kernels.hip"      // single translation unit: kernels + host ABI
 #include "irbpp_wide.hip"         // action grids of 17 .. 32 cells a side: the capacity path
 #include "irbpp_replay.hip"
+#include "irbpp_metrics.hip"        // the trainer's episode metrics (irbpp_set_episode_window)
 #include "irbpp_itemgen.h"
 
 using namespace irbpp;
@@ -47,6 +48,7 @@ struct irbpp_env {
     hipStream_t cap_stream = nullptr;
     uint64_t graph_clock = 0, graph_replays = 0;
     int obs_epoch = 0;                     // bumped by every (un)registration of an observation buffer: part of a graph's key
+    irbpp_episode_window window{};         // irbpp_set_episode_window (window.window == 0: none attached)
 };
 
 #define HIP_TRY(expr)                                   \
@@ -863,6 +865,8 @@ int irbpp_reset_bins(irbpp_env* env, const int32_t* bins_dev, int32_t count, flo
 int irbpp_step(irbpp_env* env, const int32_t* actions_dev, float* obs_dev, const irbpp_step_out* out, void* stream) {
     if (!env || !actions_dev || !obs_dev) return IRBPP_ERR_ARG;
     if (!env->was_reset) return IRBPP_ERR_STATE;
+    const bool windowed = env->window.window > 0;
+    if (windowed && (!out || !out->done_dev || !out->ep_reward_dev || !out->ratio_dev || !out->counter_dev)) return IRBPP_ERR_ARG;
     StepIO io;
     memset(&io, 0, sizeof(io));
     io.actions = actions_dev;
@@ -890,7 +894,14 @@ int irbpp_step(irbpp_env* env, const int32_t* actions_dev, float* obs_dev, const
     } else {
         env->err_mirror = nullptr;
     }
-    return launch_env(env, io, MODE_STEP, stream);
+    const int rc = launch_env(env, io, MODE_STEP, stream);
+    if (rc != IRBPP_OK || !windowed) return rc;
+    // the episode window (irbpp_metrics.hip): one workgroup behind the step's kernels, reading the outputs they wrote
+    const irbpp_episode_window& w = env->window;
+    hipLaunchKernelGGL(irbpp_window_update_kernel, dim3(1), dim3(WINDOW_UPDATE_THREADS), 0, (hipStream_t)stream, out->done_dev,
+                       out->ep_reward_dev, out->ratio_dev, out->counter_dev, env->P.N, env->cfg.global_offset, w.ring_dev,
+                       w.snapshot_dev, w.rows_dev, w.state_dev, w.window, w.history);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
 }
 
 int irbpp_get_action_candidates(irbpp_env* env, const int32_t* order_actions_dev, float* loc_obs_dev, void* stream) {
@@ -1060,6 +1071,38 @@ int irbpp_set_placement_log(irbpp_env* env, uint32_t* meta_dev, double* z_dev, i
     env->S.log_z = z_dev;
     env->S.log_cap = meta_dev ? capacity : 0;
     return IRBPP_OK;
+}
+
+int irbpp_set_episode_window(irbpp_env* env, const irbpp_episode_window* w) {
+    if (!env) return IRBPP_ERR_ARG;
+    if (w == nullptr) { env->window = irbpp_episode_window{}; return IRBPP_OK; }
+    if (!w->ring_dev || !w->snapshot_dev || !w->rows_dev || !w->state_dev || w->window < 1 || w->window > WINDOW_MAX ||
+        w->history < 1)
+        return IRBPP_ERR_ARG;
+    env->window = *w;
+    return IRBPP_OK;
+}
+
+int irbpp_episode_metrics(const irbpp_episode_window* parts, int32_t n_parts, int32_t first_step, int32_t n_steps,
+                          double* out_dev, void* stream) {
+    if (!parts || !out_dev || n_parts < 1 || n_parts > WINDOW_PARTS_MAX || first_step < 1) return IRBPP_ERR_ARG;
+    WindowParts wp;
+    memset(&wp, 0, sizeof wp);
+    wp.P = n_parts;
+    wp.W = parts[0].window;
+    wp.H = parts[0].history;
+    if (wp.W < 1 || wp.W > WINDOW_MAX || wp.H < 1 || n_steps < 1 || n_steps > wp.H) return IRBPP_ERR_ARG;
+    for (int p = 0; p < n_parts; ++p) {
+        if (!parts[p].snapshot_dev || !parts[p].rows_dev || !parts[p].state_dev || parts[p].window != wp.W ||
+            parts[p].history != wp.H)
+            return IRBPP_ERR_ARG;
+        wp.snap[p] = parts[p].snapshot_dev;
+        wp.rows[p] = parts[p].rows_dev;
+        wp.state[p] = parts[p].state_dev;
+    }
+    hipLaunchKernelGGL(irbpp_window_metrics_kernel, dim3(n_steps), dim3(64), (size_t)3 * wp.W * sizeof(double), (hipStream_t)stream,
+                       wp, first_step, out_dev);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
 }
 
 int irbpp_sumtree_find(const float* tree_dev, int32_t n_env, int32_t capacity, const float* values_dev, int32_t draws,

@@ -4,7 +4,9 @@ Bins are independent, so rank r simply owns the global bins
 [r*n, (r+1)*n).  The trajectory of global bin g in episode e is
 (traj_start + g + e*global_bins) % n_traj, which makes every result independent of the world
 size.  The only exchange is the episode statistics for logging (trainer.py:215-222): one
-all-reduce of four doubles over RCCL (backend "nccl" on ROCm; "gloo" in the CPU tests)."""
+all-reduce of four doubles over RCCL (backend "nccl" on ROCm; "gloo" in the CPU tests), or, for the
+trainer's windowed metrics (metrics.EpisodeMetrics.read(group=...)), one all_gather of the ranks'
+window buffers when the rows are read -- never a collective per step."""
 from __future__ import annotations
 
 import os
@@ -54,6 +56,20 @@ def reduce_totals(totals: torch.Tensor) -> torch.Tensor:
     if _active():
         _all_reduce(totals, dist.ReduceOp.SUM)
     return totals
+
+
+def gather_windows(buffers: torch.Tensor, group=None) -> torch.Tensor:
+    """The ranks' episode-window buffers (metrics.EpisodeMetrics.buffers: int64 [parts, words], the same shape on every rank)
+    as one [world * parts, words] tensor in rank order -- global bin order under shard() -- with ONE all_gather.  Without a
+    process group: the buffers themselves."""
+    if not _active():
+        return buffers
+    world = dist.get_world_size(group)
+    src = buffers.contiguous()
+    staged = src.cpu() if dist.get_backend(group) == "gloo" and src.is_cuda else src
+    out = [torch.empty_like(staged) for _ in range(world)]
+    dist.all_gather(out, staged, group=group)
+    return torch.cat(out).to(buffers.device)
 
 
 def max_over_ranks(value: float, device) -> float:

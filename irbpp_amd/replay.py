@@ -362,7 +362,8 @@ def actor_step(envs, policy, memory: VectorReplayMemory, state: torch.Tensor, re
     """One iteration of the trainer's acting loop (trainer.py:160-186) without per-env Python:
     mask -> policy -> envs.step -> clip -> append.  ``envs`` is a GpuPackingEnv (device-tensor
     API); ``policy(state, mask) -> int64[N]`` stands for Agent.act.  Returns the next state and
-    (reward, done) device tensors; episode statistics stay on the device (episode_totals)."""
+    (reward, done) device tensors.  The trainer's logged episode metrics (trainer.py:168-178, 215-222) stay on the device
+    too when an irbpp_amd.metrics.EpisodeMetrics window is attached to ``envs``: read its rows every few hundred steps."""
     mask = mask_from_state(state, envs.S)
     action = policy(state, mask)
     next_state, reward, done = envs.step(action if action.dtype == torch.int32 else action.to(torch.int32))
