@@ -201,6 +201,34 @@ int irbpp_reset_bins(irbpp_env* env, const int32_t* bins_dev, int32_t count, flo
 int irbpp_step(irbpp_env* env, const int32_t* actions_dev, float* obs_dev,
                const irbpp_step_out* out, void* stream);
 
+/* irbpp_step with the placement's cell handed in instead of a candidate row: PackingGame.step (binPhy.py:248-337) with
+ * candidates[action][0:3] replaced by cells_dev[b] = (rot, lx, ly), int32[num_bins][3] -- for callers that choose from the
+ * possible-position grids (Space.get_heuristic_action, search, scripted curricula), whose cell is often no contour vertex
+ * and so no candidate row.  Everything else is irbpp_step: prejudge on the extents and on np.sum(naiveMask) == 0, the drop
+ * height posZmap[rot, lx, ly] of the last observation (recomputed from the footprint's bottom cells where the observation
+ * did not mark the cell valid), simulateHeight, heightmap update, reward / done / info, auto-reset, queue update, the next
+ * (online) or order (buffered, after irbpp_get_action_candidates) observation, placement log, episode window, totals.
+ * A triple outside 0 <= rot < n_rot, 0 <= lx < Ax, 0 <= ly < Ay is the reference's IndexError: it raises
+ * IRBPP_DEVERR_BAD_ACTION and the step runs on the clamped cell.  Unlike row indices, negative values do NOT count from the
+ * end (numpy's wrap-around is not reproduced for cells).
+ * Always runs as the apply kernel followed by the observation, at every launch size and on both pipelines; configurations
+ * that apply the step inside the transition kernel answer IRBPP_ERR_ARG: stability != 0, IRBPP_TUNE_FUSED_APPLY,
+ * IRBPP_TUNE_CHAIN (where it takes effect). */
+int irbpp_step_cells(irbpp_env* env, const int32_t* cells_dev, float* obs_dev,
+                     const irbpp_step_out* out, void* stream);
+
+/* One placement of the reference's heuristic baselines without a host round trip: per bin the cell
+ * Space.get_heuristic_action (space.py:162-218) picks -- method and dir_idx as for irbpp_heuristic_action -- then
+ * irbpp_step_cells on it.  MINZ, DBLF and FIRSTFIT score the posZmap / naiveMask grids the last observation stored (one
+ * wave per bin, fused with the placement) on both pipelines; HM (16 x 16 grids only: IRBPP_ERR_ARG on the capacity path)
+ * runs irbpp_heuristic_action's scorer in front of the cell step.  Same IRBPP_ERR_ARG cases as irbpp_step_cells.
+ * The stored grids must be current: IRBPP_ERR_STATE after irbpp_set_heightmaps (it clears them), and in a buffered
+ * environment after irbpp_reset / irbpp_step, until the next observation of all bins (irbpp_reset or irbpp_step online,
+ * irbpp_get_action_candidates buffered; irbpp_get_all_possible_observation counts as well: after it the grids, the item and
+ * np.sum(naiveMask) the step goes by are those of the LAST buffer slot, as for irbpp_step). */
+int irbpp_heuristic_step(irbpp_env* env, int32_t method, int32_t dir_idx, float* obs_dev,
+                         const irbpp_step_out* out, void* stream);
+
 /* replaces: ShmemVecEnv.get_action_candidates (shmem_vec_env.py:99-102) ->
  * PackingGame.get_action_candidates (binPhy.py:161-169).  order_actions_dev: int32[num_bins]
  * buffer slots; loc_obs_dev: float32[num_bins][obs_len(1)].  Hierarchical mode only. */
@@ -453,7 +481,8 @@ int irbpp_device_error(irbpp_env* env, void* stream, int32_t* flags_out);
                                           share of the bins): results of that step are incomplete                */
 #define IRBPP_DEVERR_BAD_ACTION   64   /* irbpp_step / irbpp_get_action_candidates: an action outside [-S, S) (order action: [-k, k)):
                                           the reference raises IndexError at binPhy.py:235 / :163; a negative index in
-                                          range counts from the end, as there.  The step ran on a clamped index       */
+                                          range counts from the end, as there.  The step ran on a clamped index.
+                                          irbpp_step_cells: a cell outside the action grid (no wrap-around)           */
 #define IRBPP_DEVERR_STREAM_DRY   32   /* item_stream = 1: a bin fetched a ring slot it had consumed already and the host
                                           had not rewritten (irbpp_stream_write): its episode got no item there  */
 

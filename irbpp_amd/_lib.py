@@ -68,6 +68,8 @@ SIGNATURES = {
     "irbpp_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "irbpp_reset_bins": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "irbpp_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IrbppStepOut), C.c_void_p]),
+    "irbpp_step_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IrbppStepOut), C.c_void_p]),
+    "irbpp_heuristic_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(IrbppStepOut), C.c_void_p]),
     "irbpp_get_action_candidates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "irbpp_get_all_possible_observation": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "irbpp_policy_minz": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),

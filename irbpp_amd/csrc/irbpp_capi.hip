@@ -49,6 +49,8 @@ struct irbpp_env {
     uint64_t graph_clock = 0, graph_replays = 0;
     int obs_epoch = 0;                     // bumped by every (un)registration of an observation buffer: part of a graph's key
     irbpp_episode_window window{};         // irbpp_set_episode_window (window.window == 0: none attached)
+    int32_t* heur_cells = nullptr;         // [N][3] irbpp_heuristic_step: the cells a scorer kernel chose, read by irbpp_apply_cells_kernel
+    bool grids_current = false;            // w_posz / w_valid of EVERY bin are those of the item its next step places, on its present heightmap
 };
 
 #define HIP_TRY(expr)                                   \
@@ -260,6 +262,7 @@ int irbpp_create(const irbpp_config* cfg, irbpp_env** out) {
     P.heavy_thr = (P.S * 3) / 5;                          // (with the run-level start filter a > S bin has >= 0.70 S starts + isolated pixels, 99 % of the others < 0.65 S)
     ALLOC(w_heavy, 2 * (size_t)(XCD_STRIDE + P.heavy_cap));
 #undef ALLOC
+    if (rc == IRBPP_OK) rc = dev_alloc(env, &env->heur_cells, N * 3);
     if (rc != IRBPP_OK) { irbpp_destroy(env); return rc; }
     {   // identity launch order until an ordering pass writes another one
         std::vector<int32_t> ident(N);
@@ -637,9 +640,32 @@ static bool chain_launch(const irbpp_env* env, int n) {
     return true;
 }
 
+// The apply phase of a split step over n launch slots: a wave per bin, or (buffered environments below 2048 bins) a workgroup per
+// bin; `key` says where the placements' cells come from (ApplyKey: candidate rows, the caller's cells, the heuristic's choice).
+// irbpp_heuristic_step's selection is fused into the placing wave (irbpp_apply_heur_kernel) for MINZ / DBLF / FIRSTFIT (as a kernel
+// of its own in front of the cell apply it measured slower at every size, DESIGN.md "Placing at grid cells"); HM keeps the
+// recomputing scorer (it needs the heightmap window sums): it writes the triples to env->heur_cells, which
+// irbpp_apply_cells_kernel reads behind it on the same stream.  The scorer indexes bins by workgroup, without block_off: a
+// heuristic step always covers the whole environment (launch_env refuses any other grid for KEY_HEUR).
+static void launch_apply(irbpp_env* env, StepIO io, int mode, hipStream_t st, int n, int key) {
+    if (key == KEY_HEUR && io.heur_method == 4) {
+        StepIO sel = io;
+        sel.heur_out = env->heur_cells;
+        hipLaunchKernelGGL(irbpp_heuristic_kernel, dim3(env->P.N), dim3(256), env->P.lds_bytes_full, st, env->P, env->T, env->S, sel);
+        io.actions = env->heur_cells;
+        key = KEY_CELLS;
+    }
+    const bool wg = env->P.K > 1 && n < 2048;
+    env_kernel_fn fn = wg ? irbpp_apply_wg_kernel : irbpp_apply_kernel;
+    if (key == KEY_CELLS) fn = wg ? irbpp_apply_cells_wg_kernel : irbpp_apply_cells_kernel;
+    if (key == KEY_HEUR) fn = wg ? irbpp_apply_heur_wg_kernel : irbpp_apply_heur_kernel;
+    hipLaunchKernelGGL(fn, wg ? dim3(n) : dim3((n + 3) / 4), dim3(256), 0, st, env->P, env->T, env->S, io, mode);
+}
+
 // One launch group: the launch slots [first, first + n) of a transition -- order (for step / candidates), the
 // transition kernel and, in the split pipeline, trace and emit -- on one stream.
-static void launch_group(irbpp_env* env, StepIO io, int mode, hipStream_t st, int first, int n) {
+// key != KEY_CAND (irbpp_step_cells / irbpp_heuristic_step): always the apply kernel followed by MODE_OBSERVE, whatever the size.
+static void launch_group(irbpp_env* env, StepIO io, int mode, hipStream_t st, int first, int n, int key = KEY_CAND) {
     io.block_off = first;
     io.n_slots = n;
     io.auto_action = env->auto_actions;
@@ -662,8 +688,7 @@ static void launch_group(irbpp_env* env, StepIO io, int mode, hipStream_t st, in
     if (env->P.wide) {                     // irbpp_wide.hip: [the geometry-free apply kernel,] then ONE kernel per observation
         int wmode = mode;
         if (mode == MODE_STEP) {
-            if (env->P.K > 1 && n < 2048) hipLaunchKernelGGL(irbpp_apply_wg_kernel, dim3(n), dim3(256), 0, st, env->P, env->T, env->S, io, mode);
-            else hipLaunchKernelGGL(irbpp_apply_kernel, dim3((n + 3) / 4), dim3(256), 0, st, env->P, env->T, env->S, io, mode);
+            launch_apply(env, io, mode, st, n, key);
             if (env->P.K > 1) return;
             wmode = MODE_OBSERVE;
         }
@@ -686,12 +711,11 @@ static void launch_group(irbpp_env* env, StepIO io, int mode, hipStream_t st, in
                            env->P, env->T, env->S, io, mode);
         return;
     }
-    if (mode == MODE_STEP && split_apply(env, n)) {
+    if (mode == MODE_STEP && (key != KEY_CAND || split_apply(env, n))) {
         // a buffered step: a workgroup per bin at launches of fewer than 2048 bins (a wave per bin leaves most of the chip
         // to one dependent chain per CU there: 15.7 vs 15.3 M at 1024 bins), a wave per bin from there on (every bin resident
         // at once: 8192 bins as two groups 50.6 -> 55.2 M, 4096 bins 40.0 -> 41.6 M; profiles/r05/s27)
-        if (env->P.K > 1 && n < 2048) hipLaunchKernelGGL(irbpp_apply_wg_kernel, dim3(n), dim3(256), 0, st, env->P, env->T, env->S, io, mode);
-        else hipLaunchKernelGGL(irbpp_apply_kernel, dim3((n + 3) / 4), dim3(256), 0, st, env->P, env->T, env->S, io, mode);
+        launch_apply(env, io, mode, st, n, key);
         env_mode = MODE_OBSERVE;         // (a buffered step ends with the apply kernel: it wrote the order observation)
     }
     if (!(env_mode == MODE_OBSERVE && env->P.K > 1)) {
@@ -763,8 +787,9 @@ static void drop_graphs(irbpp_env* env) {
 }
 static bool graph_wanted(const irbpp_env* env, int) { return (env->cfg.tuning & IRBPP_TUNE_GRAPH) != 0; }
 
-static int launch_env(irbpp_env* env, StepIO io, int mode, void* stream, int grid = 0) {
+static int launch_env(irbpp_env* env, StepIO io, int mode, void* stream, int grid = 0, int key = KEY_CAND) {
     if (grid <= 0) grid = env->P.N;
+    if (key == KEY_HEUR && grid != env->P.N) return IRBPP_ERR_ARG;     // (HM's scorer covers all bins: launch_apply)
     io.phase_cycles = env->phase_cycles;
     hipStream_t st = (hipStream_t)stream;
     size_t pairs = env->timing.size() / 2;
@@ -772,7 +797,7 @@ static int launch_env(irbpp_env* env, StepIO io, int mode, void* stream, int gri
     if (pairs && (env->timing_phase++ % env->timing_every) != 0) pairs = 0;       // not a sampled launch
     if (pairs) hipEventRecord(env->timing[2 * slot], st);
     bool launched = false;
-    if (graph_wanted(env, grid) && (mode == MODE_STEP || mode == MODE_CANDS)) {
+    if (graph_wanted(env, grid) && (mode == MODE_STEP || mode == MODE_CANDS) && key == KEY_CAND) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(st, &cs) != hipSuccess) cs = hipStreamCaptureStatusActive;
         if (cs == hipStreamCaptureStatusNone) {
@@ -826,13 +851,20 @@ static int launch_env(irbpp_env* env, StepIO io, int mode, void* stream, int gri
             }
         }
     }
-    if (!launched) launch_group(env, io, mode, st, 0, grid);
+    if (!launched) launch_group(env, io, mode, st, 0, grid, key);
     if (pairs) {
         hipEventRecord(env->timing[2 * slot + 1], st);
         env->timing_next = (slot + 1) % pairs;
         if (env->timing_used < pairs) env->timing_used++;
     }
-    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+    if (hipGetLastError() != hipSuccess) return IRBPP_ERR_HIP;
+    // are the grids of the last observation (w_posz / w_valid) those of the item every bin places next?  A launch over all
+    // bins that observes makes them so (MODE_CANDS of irbpp_get_all_possible_observation too: the grids are the last slot's,
+    // and so are BinState::cur_item / nvalid, which the selection and prejudge go by); a buffered step or reset moves the
+    // heightmap / the queue on without observing.  Only launches that went out count.
+    if (io.bin_list == nullptr && mode != MODE_POSSIBLE)
+        env->grids_current = mode == MODE_CANDS || env->P.K == 1;
+    return IRBPP_OK;
 }
 
 int irbpp_reset(irbpp_env* env, float* obs_dev, void* stream) {
@@ -862,14 +894,17 @@ int irbpp_reset_bins(irbpp_env* env, const int32_t* bins_dev, int32_t count, flo
     return launch_env(env, io, MODE_RESET, stream, count);
 }
 
-int irbpp_step(irbpp_env* env, const int32_t* actions_dev, float* obs_dev, const irbpp_step_out* out, void* stream) {
-    if (!env || !actions_dev || !obs_dev) return IRBPP_ERR_ARG;
-    if (!env->was_reset) return IRBPP_ERR_STATE;
+// irbpp_step and its two siblings: `key` says what actions_dev holds (KEY_CAND: candidate rows; KEY_CELLS: int32[N][3] cells;
+// KEY_HEUR: nothing, the heuristic (method, dir_idx) chooses)
+static int step_common(irbpp_env* env, const int32_t* actions_dev, float* obs_dev, const irbpp_step_out* out, void* stream, int key,
+                       int method = 0, int dir_idx = 0) {
     const bool windowed = env->window.window > 0;
     if (windowed && (!out || !out->done_dev || !out->ep_reward_dev || !out->ratio_dev || !out->counter_dev)) return IRBPP_ERR_ARG;
     StepIO io;
     memset(&io, 0, sizeof(io));
     io.actions = actions_dev;
+    io.heur_method = method;
+    io.heur_dir = dir_idx;
     io.obs = obs_dev;
     io.obs_stride = env->P.obs_len0;
     if (out) {
@@ -894,7 +929,7 @@ int irbpp_step(irbpp_env* env, const int32_t* actions_dev, float* obs_dev, const
     } else {
         env->err_mirror = nullptr;
     }
-    const int rc = launch_env(env, io, MODE_STEP, stream);
+    const int rc = launch_env(env, io, MODE_STEP, stream, 0, key);
     if (rc != IRBPP_OK || !windowed) return rc;
     // the episode window (irbpp_metrics.hip): one workgroup behind the step's kernels, reading the outputs they wrote
     const irbpp_episode_window& w = env->window;
@@ -902,6 +937,31 @@ int irbpp_step(irbpp_env* env, const int32_t* actions_dev, float* obs_dev, const
                        out->ep_reward_dev, out->ratio_dev, out->counter_dev, env->P.N, env->cfg.global_offset, w.ring_dev,
                        w.snapshot_dev, w.rows_dev, w.state_dev, w.window, w.history);
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+int irbpp_step(irbpp_env* env, const int32_t* actions_dev, float* obs_dev, const irbpp_step_out* out, void* stream) {
+    if (!env || !actions_dev || !obs_dev) return IRBPP_ERR_ARG;
+    if (!env->was_reset) return IRBPP_ERR_STATE;
+    return step_common(env, actions_dev, obs_dev, out, stream, KEY_CAND);
+}
+
+// a step whose placement does not come from a candidate row is always the apply kernel + MODE_OBSERVE: configurations that
+// apply inside the transition kernel cannot take it
+static bool applies_in_transition(const irbpp_env* env) {
+    return env->P.stability != 0 || (env->cfg.tuning & IRBPP_TUNE_FUSED_APPLY) || chain_launch(env, env->P.N);
+}
+
+int irbpp_step_cells(irbpp_env* env, const int32_t* cells_dev, float* obs_dev, const irbpp_step_out* out, void* stream) {
+    if (!env || !cells_dev || !obs_dev || applies_in_transition(env)) return IRBPP_ERR_ARG;
+    if (!env->was_reset) return IRBPP_ERR_STATE;
+    return step_common(env, cells_dev, obs_dev, out, stream, KEY_CELLS);
+}
+
+int irbpp_heuristic_step(irbpp_env* env, int32_t method, int32_t dir_idx, float* obs_dev, const irbpp_step_out* out, void* stream) {
+    if (!env || !obs_dev || method < 1 || method > 4 || dir_idx < 0 || dir_idx > 3 || applies_in_transition(env)) return IRBPP_ERR_ARG;
+    if (method == 4 && env->P.wide) return IRBPP_ERR_ARG;          // HM: the recomputing scorer, which the capacity path lacks
+    if (!env->was_reset || !env->grids_current) return IRBPP_ERR_STATE;
+    return step_common(env, nullptr, obs_dev, out, stream, KEY_HEUR, method, dir_idx);
 }
 
 int irbpp_get_action_candidates(irbpp_env* env, const int32_t* order_actions_dev, float* loc_obs_dev, void* stream) {
@@ -1055,6 +1115,7 @@ int irbpp_set_heightmaps(irbpp_env* env, const double* hm_dev, void* stream) {
     // the drop heights of the last observation (w_posz, marked by w_valid) belong to the OLD maps: a step that follows
     // without a new observation recomputes its drop height from the footprint's bottom cells instead
     HIP_TRY(hipMemsetAsync(env->S.w_valid, 0, (size_t)env->P.N * env->P.R * env->P.vrow * sizeof(uint32_t), (hipStream_t)stream));
+    env->grids_current = false;            // (irbpp_heuristic_step answers IRBPP_ERR_STATE until the next observation of all bins)
     return IRBPP_OK;
 }
 

@@ -3046,7 +3046,69 @@ __device__ __forceinline__ void env_transition(const Params& P_run, const Tables
 // PER_WORKGROUP (buffered environments): a WORKGROUP per bin -- wave 0 applies the action exactly as below, then all four waves
 // write the order observation (the tile's 1024 ... 4096 cells as float32: one wave alone took 16 ... 64 dependent round trips
 // for it, which is what made the wave-per-bin form lose for K > 1).
-template <bool PER_WORKGROUP>
+// KEY: where the placement's (rot, lx, ly) comes from -- KEY_CAND: candidate row io.actions[b] of the last observation (irbpp_step);
+// KEY_CELLS: the triple io.actions[3 b ..] itself (irbpp_step_cells); KEY_HEUR: the cell Space.get_heuristic_action picks on the
+// grids the last observation left in w_posz / w_valid (irbpp_heuristic_step, selection fused into the placing wave).  A
+// compile-time choice: the builds of irbpp_step carry nothing of the other two.
+enum ApplyKey : int { KEY_CAND = 0, KEY_CELLS = 1, KEY_HEUR = 2 };
+
+// Space.get_heuristic_action (space.py:162-218) for MINZ, DBLF and FIRSTFIT by ONE WAVE, from what the last observation of bin b
+// stored: posZmap where naiveMask is set (w_posz) and naiveMask as bit rows (w_valid) -- 8 bytes per action cell read back, no
+// overlap test (irbpp_heuristic_kernel repeats it on an LDS tile with a workgroup per bin; HM, which needs the heightmap
+// window sums, stays there).  Scores in float64 in the reference's order of operations, invalid cells 1e6, np.round(., 6), the
+// first minimum in C order (rot, X, Y): a lane meets its cells in ascending index order and keeps the first of equals, the
+// butterfly compares (score, index).  Returns rot << 16 | lx << 8 | ly, the same in every lane.  Independent of the LDS
+// layouts: serves the capacity path too (P.vrow words per rotation).
+__device__ __forceinline__ uint32_t heuristic_select_wave(const Params& P, const State& S, int method, int dir, int b, int lane) {
+    const int RAC = P.R * P.AC;
+    const double* const zsrc = S.w_posz + (size_t)b * RAC;
+    const uint32_t* const vsrc = S.w_valid + (size_t)b * P.R * P.vrow;
+    const bool xf = (dir & 2) != 0, yf = (dir & 1) != 0;
+    double best = 1e300;
+    int best_i = 0x7fffffff;
+    for (int i0 = 0; i0 < RAC; i0 += 4 * 64) {                        // four cells per lane in flight
+        int X[4], Y[4];
+        uint32_t vw[4];
+        double z[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int idx = i0 + u * 64 + lane, ii = idx < RAC ? idx : 0;
+            const int r = fdiv(ii, P.AC, P.mg_ac), c = ii - r * P.AC;
+            X[u] = fdiv(c, P.Ay, P.mg_ay);
+            Y[u] = c - X[u] * P.Ay;
+            vw[u] = vsrc[r * P.vrow + X[u]];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int idx = i0 + u * 64 + lane;
+            z[u] = 1e3;
+            if (idx < RAC && ((vw[u] >> Y[u]) & 1u)) z[u] = zsrc[idx];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int idx = i0 + u * 64 + lane;
+            if (idx >= RAC) continue;
+            double sc = 1e6;                                           // score[invalidIndex] = 1e6 (space.py:200)
+            if ((vw[u] >> Y[u]) & 1u) {
+                const double cx = xf ? (double)(P.Ax - X[u]) : (double)X[u], cy = yf ? (double)(P.Ay - Y[u]) : (double)Y[u];
+                const double raw = method == 1 ? z[u] : method == 2 ? (cx + cy) * P.res_a + 100.0 * z[u] : cx + cy;
+                sc = round6(raw);
+            }
+            if (sc < best) { best = sc; best_i = idx; }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ob = __shfl_xor(best, o);
+        const int oi = __shfl_xor(best_i, o);
+        if (ob < best || (ob == best && oi < best_i)) { best = ob; best_i = oi; }
+    }
+    best_i = __builtin_amdgcn_readfirstlane(best_i);
+    const int hr = fdiv(best_i, P.AC, P.mg_ac), hrem = best_i - hr * P.AC;
+    const int hx = fdiv(hrem, P.Ay, P.mg_ay);
+    return ((uint32_t)hr << 16) | ((uint32_t)hx << 8) | (uint32_t)(hrem - hx * P.Ay);
+}
+
+template <bool PER_WORKGROUP, int KEY = KEY_CAND>
 __device__ __forceinline__ void apply_body(const Params& P, const Tables& T, const State& S, const StepIO& io) {
     const int lane = threadIdx.x & 63;
     const int slot = PER_WORKGROUP ? (int)blockIdx.x : (int)blockIdx.x * WAVES + (int)(threadIdx.x >> 6);
@@ -3056,15 +3118,35 @@ __device__ __forceinline__ void apply_body(const Params& P, const Tables& T, con
     int32_t* const q = S.queue + (size_t)b * P.K;
     if (!PER_WORKGROUP || threadIdx.x < 64) {
     // round 1: the action and the bin's scalars
-    int a = io.actions[b];
+    int a = 0, cell_r = 0, cell_x = 0, cell_y = 0;
+    if constexpr (KEY == KEY_CAND) a = io.actions[b];
+    if constexpr (KEY == KEY_CELLS) { cell_r = io.actions[3 * b]; cell_x = io.actions[3 * b + 1]; cell_y = io.actions[3 * b + 2]; }
     const BinState* ps0 = S.bs + b;
     const int item0 = ps0->cur_item, oa = ps0->order_action, nvalid0 = ps0->nvalid, nrows = ps0->nrows;
     const int cursor = ps0->cursor, trow = ps0->traj_row;
     // round 2: candidate key; ALL rotations' ShapeRots of the placed item, sixteen bytes per lane (R x 112 bytes are
     // contiguous), so that the one the key names needs no round trip of its own; its volume; the next item of the trajectory
+    uint32_t key;
+    if constexpr (KEY == KEY_CAND) {
     a += a < 0 ? P.S : 0;                                            // candidates[action] (binPhy.py:235): a negative index counts from the end
     if (a < 0 || a >= P.S) { if (lane == 0) raise_error(S, IRBPP_DEVERR_BAD_ACTION); a = a < 0 ? 0 : P.S - 1; }   // the reference's IndexError
-    const uint32_t key = (uint32_t)__builtin_amdgcn_readfirstlane(a < nrows ? (int)S.cand[(size_t)b * P.S + a] : 0);   // action_to_position (:234-236)
+    key = (uint32_t)__builtin_amdgcn_readfirstlane(a < nrows ? (int)S.cand[(size_t)b * P.S + a] : 0);   // action_to_position (:234-236)
+    } else if constexpr (KEY == KEY_CELLS) {
+        // the caller's cell in place of candidates[action][0:3]; outside the grid is the reference's IndexError at posZmap[rot, lx, ly]
+        // (binPhy.py:266) -- no negative wrap-around here: raised, and the step runs on the clamped cell
+        if (cell_r < 0 || cell_r >= P.R || cell_x < 0 || cell_x >= P.Ax || cell_y < 0 || cell_y >= P.Ay) {
+            if (lane == 0) raise_error(S, IRBPP_DEVERR_BAD_ACTION);
+            cell_r = cell_r < 0 ? 0 : cell_r >= P.R ? P.R - 1 : cell_r;
+            cell_x = cell_x < 0 ? 0 : cell_x >= P.Ax ? P.Ax - 1 : cell_x;
+            cell_y = cell_y < 0 ? 0 : cell_y >= P.Ay ? P.Ay - 1 : cell_y;
+        }
+        key = (uint32_t)__builtin_amdgcn_readfirstlane((cell_r << 16) | (cell_x << 8) | cell_y);
+        (void)nrows;
+    } else {
+        // naiveMask all zero (or no item): every score is 1e6 and np.argmin answers cell (0, 0, 0), which prejudge then refuses
+        key = (item0 >= 0 && nvalid0 > 0) ? heuristic_select_wave(P, S, io.heur_method, io.heur_dir, b, lane) : 0u;
+        (void)nrows;
+    }
     int nxt = -2;
     if (P.K == 1) {
         const int at = T.stream ? (int)((uint32_t)cursor % (uint32_t)T.seq_len) : cursor;
@@ -3244,6 +3326,16 @@ extern "C" __global__ void __launch_bounds__(BLOCK)
 irbpp_apply_kernel(const Params P, const Tables T, const State S, const StepIO io, const int mode) { apply_body<false>(P, T, S, io); }
 extern "C" __global__ void __launch_bounds__(BLOCK)
 irbpp_apply_wg_kernel(const Params P, const Tables T, const State S, const StepIO io, const int mode) { apply_body<true>(P, T, S, io); }
+// irbpp_step_cells: the same step with the placement's cell handed in (io.actions = int32[N][3]: rot, lx, ly) ...
+extern "C" __global__ void __launch_bounds__(BLOCK)
+irbpp_apply_cells_kernel(const Params P, const Tables T, const State S, const StepIO io, const int mode) { apply_body<false, KEY_CELLS>(P, T, S, io); }
+extern "C" __global__ void __launch_bounds__(BLOCK)
+irbpp_apply_cells_wg_kernel(const Params P, const Tables T, const State S, const StepIO io, const int mode) { apply_body<true, KEY_CELLS>(P, T, S, io); }
+// ... and irbpp_heuristic_step: chosen by the placing wave itself (io.heur_method / heur_dir; MINZ, DBLF, FIRSTFIT)
+extern "C" __global__ void __launch_bounds__(BLOCK)
+irbpp_apply_heur_kernel(const Params P, const Tables T, const State S, const StepIO io, const int mode) { apply_body<false, KEY_HEUR>(P, T, S, io); }
+extern "C" __global__ void __launch_bounds__(BLOCK)
+irbpp_apply_heur_wg_kernel(const Params P, const Tables T, const State S, const StepIO io, const int mode) { apply_body<true, KEY_HEUR>(P, T, S, io); }
 
 // Launch order of an online step on the generic path: bins that are about to observe the SAME item run on the same
 // die, one after the other.  The item a bin observes next is known before the step (the next entry of its trajectory;

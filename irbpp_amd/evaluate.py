@@ -33,7 +33,7 @@ def rotation_quaternion_xyzw(rot_idx: int) -> np.ndarray:
 def evaluate(shapes, sequences, n_episodes: int, *, policy: Optional[Callable] = None,
              order_policy: Optional[Callable] = None, device="cuda:0",
              names: Optional[Dict[int, str]] = None, traj_start: int = 1, max_steps: int = 4096,
-             log_capacity: int = 256, save: Optional[str] = None, **env_kw):
+             log_capacity: int = 256, save: Optional[str] = None, heuristic=None, **env_kw):
     """Run ``n_episodes`` evaluation episodes, one per bin.
 
     ``policy(env, loc_obs) -> int32[N] device tensor`` picks the location actions; default = the scripted MINZ
@@ -41,6 +41,9 @@ def evaluate(shapes, sequences, n_episodes: int, *, policy: Optional[Callable] =
     -> int32[N]`` picks the buffer slot (orderDQN.act; default slot 0), ``get_action_candidates`` builds the location
     observation of that item (binPhy.py:161-169), ``policy`` acts on it, ``step`` places the item and refills the
     queue (update_item_queue + generate_item, binPhy.py:324-325).
+    ``heuristic=("DBLF", 0)`` (method, dirIdx): the reference's heuristic baseline instead of ``policy`` -- every placement
+    is ``heuristic_step``, the cell Space.get_heuristic_action picks on the possible-position grids (space.py:162-218),
+    which is often no candidate row; buffered sets still choose the slot with ``order_policy``.
     Returns a dict with the statistics ``tools.test`` prints and ``trajs``: a list
     over episodes of ``env.packed`` (binPhy.py:296), i.e. one row ``[item_id, name, positionFLB(3),
     quaternion_xyzw(4)]`` per placement INCLUDING the refused one that ended the episode (the reference
@@ -63,10 +66,16 @@ def evaluate(shapes, sequences, n_episodes: int, *, policy: Optional[Callable] =
     pick = policy if policy is not None else (lambda e, o: e.policy_minz(o))
     slot0 = torch.zeros((n,), dtype=torch.int32, device=env.device)
     pick_order = order_policy if order_policy is not None else (lambda e, o: slot0)
+    if heuristic is not None:
+        if policy is not None:
+            raise ValueError("evaluate: give either policy or heuristic")
+        method, dir_idx = (heuristic, 0) if isinstance(heuristic, str) else heuristic
     for _ in range(max_steps):
         if env.K > 1:                                     # tools.py:379-388
             loc = env.get_action_candidates(pick_order(env, obs).to(torch.int32))
-            obs, _, _ = env.step(pick(env, loc))
+            obs, _, _ = env.heuristic_step(method, dir_idx) if heuristic is not None else env.step(pick(env, loc))
+        elif heuristic is not None:
+            obs, _, _ = env.heuristic_step(method, dir_idx)
         else:
             obs, _, _ = env.step(pick(env, obs))
         h = env.step_info_host()

@@ -160,6 +160,29 @@ class GpuPackingEnv(object):
                    "irbpp_step")
         return obs, self._out_f64[0], self._out_done
 
+    def step_cells(self, cells: torch.Tensor, obs_out: Optional[torch.Tensor] = None, stream=None):
+        """``step`` with the placement's cell handed in: cells int32[N, 3] = (rot, lx, ly) on the device, in place of a
+        candidate row (irbpp_step_cells) -- for callers that choose from the possible-position grids, like
+        ``heuristic_action``.  Returns what ``step`` returns.  A cell outside the action grid raises BAD_ACTION through
+        ``step_info_host``; not with ``stability`` or the tunings that apply inside the transition kernel."""
+        assert cells.dtype == torch.int32 and cells.is_cuda and cells.is_contiguous() and cells.shape == (self.num_bins, 3)
+        obs = obs_out if obs_out is not None else \
+            torch.empty((self.num_bins, self.obs_len), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.irbpp_step_cells(self._h, _ptr(cells), _ptr(obs), C.byref(self._step_out), self._stream(stream)),
+                   "irbpp_step_cells")
+        return obs, self._out_f64[0], self._out_done
+
+    def heuristic_step(self, method: str, dir_idx: int = 0, obs_out: Optional[torch.Tensor] = None, stream=None):
+        """One placement of the reference's heuristic baseline ``method`` ("MINZ", "DBLF", "FIRSTFIT", "HM") with flip
+        ``dir_idx`` in every bin, chosen and placed on the device (irbpp_heuristic_step) -- ``heuristic_action``
+        followed by ``step_cells`` without the triples ever leaving it.  Returns what ``step`` returns.  Needs the grids
+        of the last observation: raises after ``set_heightmaps`` and, buffered, without ``get_action_candidates``."""
+        obs = obs_out if obs_out is not None else \
+            torch.empty((self.num_bins, self.obs_len), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.irbpp_heuristic_step(self._h, self.HEURISTICS[method], int(dir_idx), _ptr(obs),
+                                                 C.byref(self._step_out), self._stream(stream)), "irbpp_heuristic_step")
+        return obs, self._out_f64[0], self._out_done
+
     def get_action_candidates(self, order_actions: torch.Tensor, obs_out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
         assert order_actions.dtype == torch.int32 and order_actions.is_cuda
         obs = obs_out if obs_out is not None else \
@@ -411,6 +434,22 @@ class GroupedPackingEnv(object):
         with torch.cuda.stream(self.streams[g]):
             return self.groups[g].step(actions, obs_out=obs_out)
 
+    def step_cells_group(self, g: int, cells: torch.Tensor, obs_out: Optional[torch.Tensor] = None, wait: bool = True):
+        """``step_group`` with cells int32[per, 3] = (rot, lx, ly) in place of candidate rows (GpuPackingEnv.step_cells)."""
+        self._enter(g, cells, obs_out, wait=wait)
+        if obs_out is not None:
+            return self.groups[g].step_cells(cells, obs_out=obs_out, stream=self.streams[g])
+        with torch.cuda.stream(self.streams[g]):
+            return self.groups[g].step_cells(cells, obs_out=obs_out)
+
+    def heuristic_step_group(self, g: int, method: str, dir_idx: int = 0, obs_out: Optional[torch.Tensor] = None, wait: bool = True):
+        """Group g places by the heuristic (GpuPackingEnv.heuristic_step), on its stream."""
+        self._enter(g, obs_out, wait=wait)
+        if obs_out is not None:
+            return self.groups[g].heuristic_step(method, dir_idx, obs_out=obs_out, stream=self.streams[g])
+        with torch.cuda.stream(self.streams[g]):
+            return self.groups[g].heuristic_step(method, dir_idx, obs_out=obs_out)
+
     def policy_minz_group(self, g: int, loc_obs: torch.Tensor, actions_out: Optional[torch.Tensor] = None, wait: bool = True):
         self._enter(g, loc_obs, actions_out, wait=wait)
         with torch.cuda.stream(self.streams[g]):
@@ -440,6 +479,22 @@ class GroupedPackingEnv(object):
             torch.empty((self.num_bins, self.obs_len), dtype=torch.float32, device=self.device)
         for g in range(self.num_groups):
             self.step_group(g, actions[self.rows(g)], obs_out=obs[self.rows(g)])
+        return obs
+
+    def step_cells(self, cells: torch.Tensor, obs_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``step`` with cells int32[num_bins, 3] in place of candidate rows, every group on its own stream (no join)."""
+        obs = obs_out if obs_out is not None else \
+            torch.empty((self.num_bins, self.obs_len), dtype=torch.float32, device=self.device)
+        for g in range(self.num_groups):
+            self.step_cells_group(g, cells[self.rows(g)], obs_out=obs[self.rows(g)])
+        return obs
+
+    def heuristic_step(self, method: str, dir_idx: int = 0, obs_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Every group places by the heuristic on its own stream (no join)."""
+        obs = obs_out if obs_out is not None else \
+            torch.empty((self.num_bins, self.obs_len), dtype=torch.float32, device=self.device)
+        for g in range(self.num_groups):
+            self.heuristic_step_group(g, method, dir_idx, obs_out=obs[self.rows(g)])
         return obs
 
     def get_action_candidates(self, order_actions: torch.Tensor, obs_out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -838,6 +893,18 @@ class GpuVecEnv(object):
 
     def step(self, actions):
         self.step_async(actions)
+        return self.step_wait()
+
+    def step_cells(self, cells):
+        """``step`` for placements given as grid cells: ``cells`` [N, 3] = (rot, lx, ly) per env (host array or tensor), e.g.
+        what Space.get_heuristic_action returns, in place of indices into the candidate rows -> (obs, reward, done, infos)."""
+        if self.waiting_step:
+            raise RuntimeError("already running an async step")
+        c = cells if isinstance(cells, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(cells))
+        c = c.reshape(self.num_envs, 3).to(device=self.device, dtype=torch.int32).contiguous()
+        res = self.env.step_cells(c, obs_out=self._next_obs())
+        self._pending = res if isinstance(res, torch.Tensor) else res[0]
+        self.waiting_step = True
         return self.step_wait()
 
     # False (default): get_action_candidates returns a host float32 array, which the unmodified trainer can wrap
