@@ -281,6 +281,9 @@ int irbpp_stream_cursors(irbpp_env* env, int32_t* cursors_dev, int32_t set, void
  * they have consumed. */
 int irbpp_stream_write(irbpp_env* env, const int32_t* ids_dev, const int32_t* first_dev, const int32_t* count_dev,
                        int32_t width, void* stream);
+/* Tests and tooling: the stream table as it stands (int32[n_traj][length], device memory; -3 in a slot its bin has
+ * consumed and nobody has rewritten).  Asynchronous on `stream`. */
+int irbpp_stream_table(irbpp_env* env, int32_t* table_dev, void* stream);
 
 /* replaces: RandomItemCreator / RandomInstanceCreator / RandomCateCreator.generate_item (IRcreator.py:26-72) of ONE
  * environment whose process was seeded with `seed` (= args.seed + rank, envs.py:41 -> binPhy.py:118-123): host-side,
@@ -293,6 +296,31 @@ int irbpp_itemgen_create(uint32_t seed, int32_t n_groups, const int32_t* group_o
                          int32_t n_members, irbpp_itemgen** out);
 int irbpp_itemgen_draw(irbpp_itemgen* gen, int32_t count, int32_t* out_host);
 int irbpp_itemgen_destroy(irbpp_itemgen* gen);
+
+/* The same streams drawn on the device, n_streams of them over one set of lists, stream s seeded seeds_host[s]
+ * (init_genrand runs on the device, launched on `stream`; the arguments are checked like irbpp_itemgen_create's).  Per
+ * stream the generator keeps the 624 key words, the position in them and `delivered`, the number of items it has
+ * written so far (64-bit), all in device memory.  Every call below is asynchronous on its `stream` and reads nothing
+ * back; calls that touch the same streams of a generator must be ordered by the caller (same HIP stream, or events).
+ *   irbpp_itemgen_dev_draw       appends `count` items of EVERY stream: out_dev = int32[n_streams][count], device memory
+ *                                (parity tests and tooling; advances the state a refill advances)
+ *   irbpp_itemgen_dev_delivered  copies `delivered` to out_dev = int64[n_streams], device memory
+ *   irbpp_stream_refill          item_stream = 1 with the table loaded, one row per bin (IRBPP_ERR_STATE / _ARG otherwise;
+ *                                IRBPP_ERR_ARG if first_stream + num_bins > n_streams): bin b is fed by stream
+ *                                s = first_stream + b.  With c the bin's cursor, w = delivered[s] and L the ring length,
+ *                                the c + L - w items the bin has consumed are drawn and written to ring slots
+ *                                (w + j) mod L, and delivered[s] grows by as many -- so the first refill of a new
+ *                                environment fills the whole ring and its table may be loaded as a placeholder of -1.
+ *                                c > w (the bin ran past what it was given) raises IRBPP_DEVERR_STREAM_DRY in the sticky
+ *                                error word and writes nothing.  No host read, no synchronisation. */
+typedef struct irbpp_itemgen_dev irbpp_itemgen_dev;
+int irbpp_itemgen_dev_create(int32_t device, int32_t n_streams, const uint32_t* seeds_host, int32_t n_groups,
+                             const int32_t* group_offsets, const int32_t* members, int32_t n_members, void* stream,
+                             irbpp_itemgen_dev** out);
+int irbpp_itemgen_dev_draw(irbpp_itemgen_dev* gen, int32_t count, int32_t* out_dev, void* stream);
+int irbpp_itemgen_dev_delivered(irbpp_itemgen_dev* gen, int64_t* out_dev, void* stream);
+int irbpp_stream_refill(irbpp_env* env, irbpp_itemgen_dev* gen, int32_t first_stream, void* stream);
+int irbpp_itemgen_dev_destroy(irbpp_itemgen_dev* gen);
 
 /* -- stage-level entry points (parity tests and tooling) ------------------------------- */
 

@@ -79,9 +79,16 @@ SIGNATURES = {
     "irbpp_invalidate_obs_buffer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "irbpp_stream_cursors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "irbpp_stream_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "irbpp_stream_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "irbpp_itemgen_create": (C.c_int, [C.c_uint32, C.c_int32, c_i32_p, c_i32_p, C.c_int32, C.POINTER(C.c_void_p)]),
     "irbpp_itemgen_draw": (C.c_int, [C.c_void_p, C.c_int32, c_i32_p]),
     "irbpp_itemgen_destroy": (C.c_int, [C.c_void_p]),
+    "irbpp_itemgen_dev_create": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_uint32), C.c_int32, c_i32_p, c_i32_p, C.c_int32,
+                                           C.c_void_p, C.POINTER(C.c_void_p)]),
+    "irbpp_itemgen_dev_draw": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "irbpp_itemgen_dev_delivered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "irbpp_stream_refill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "irbpp_itemgen_dev_destroy": (C.c_int, [C.c_void_p]),
     "irbpp_possible_position": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "irbpp_heuristic_action": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "irbpp_shot_item": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,

@@ -19,6 +19,7 @@
 #include "irbpp_kernels.hip"      // single translation unit: kernels + host ABI
 #include "irbpp_wide.hip"         // action grids of 17 .. 32 cells a side: the capacity path
 #include "irbpp_replay.hip"
+#include "irbpp_itemgen.hip"        // the item streams of irbpp_itemgen.h drawn on the device (irbpp_itemgen_dev_*, irbpp_stream_refill)
 #include "irbpp_metrics.hip"        // the trainer's episode metrics (irbpp_set_episode_window)
 #include "irbpp_itemgen.h"
 
@@ -157,7 +158,7 @@ const char* irbpp_status_string(int status) {
     }
 }
 
-int irbpp_version(void) { return 600; }      // 3xx: irbpp_config::tuning / item_stream, unregister / invalidate_obs_buffer, stream ring, itemgen; 5xx: source hash, overlap path, specialised builds
+int irbpp_version(void) { return 610; }      // 61x: device item generator (irbpp_itemgen_dev_*, irbpp_stream_refill); 3xx: irbpp_config::tuning / item_stream, unregister / invalidate_obs_buffer, stream ring, itemgen; 5xx: source hash, overlap path, specialised builds
 
 #ifndef IRBPP_SOURCE_HASH
 #define IRBPP_SOURCE_HASH "unstamped"
@@ -501,6 +502,24 @@ int irbpp_stream_write(irbpp_env* env, const int32_t* ids_dev, const int32_t* fi
     hipLaunchKernelGGL(irbpp_stream_write_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        const_cast<int32_t*>(env->T.seq), env->T.n_traj, env->T.seq_len, ids_dev, first_dev, count_dev, width);
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+int irbpp_stream_table(irbpp_env* env, int32_t* table_dev, void* stream) {
+    if (!env || !table_dev) return IRBPP_ERR_ARG;
+    if (!env->cfg.item_stream || !env->seq_loaded) return IRBPP_ERR_STATE;
+    HIP_TRY(hipMemcpyAsync(table_dev, env->T.seq, (size_t)env->T.n_traj * env->T.seq_len * sizeof(int32_t), hipMemcpyDeviceToDevice,
+                           (hipStream_t)stream));
+    return IRBPP_OK;
+}
+
+int irbpp_stream_refill(irbpp_env* env, irbpp_itemgen_dev* gen, int32_t first_stream, void* stream) {
+    if (!env || !gen || first_stream < 0) return IRBPP_ERR_ARG;
+    if (!env->cfg.item_stream || !env->seq_loaded) return IRBPP_ERR_STATE;
+    if ((long long)first_stream + env->P.N > gen->n_streams) return IRBPP_ERR_ARG;
+    if (env->T.n_traj != env->P.N || gen->device != env->cfg.device) return IRBPP_ERR_ARG;   // a ring per bin, on the generator's device
+    env->err_mirror = nullptr;                    // (as irbpp_stream_write; a STREAM_DRY raised here reaches S.err, which seeds the next step's word)
+    return irbpp::itemgen_launch_refill(gen, env->S.bs, const_cast<int32_t*>(env->T.seq), env->P.N, env->T.seq_len, first_stream,
+                                        env->S.err, (hipStream_t)stream);
 }
 
 int irbpp_obs_len(const irbpp_env* env, int32_t which) {

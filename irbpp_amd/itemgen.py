@@ -6,6 +6,8 @@ generator (RandomItemCreator / RandomInstanceCreator / RandomCateCreator, IRcrea
 bit for bit (host code of libirbpp_hip.so: csrc/irbpp_itemgen.h); ``StreamFeeder`` keeps the per-bin item rings of an
 environment created with ``item_stream=1`` ahead of the bins, so that ``make_vec_envs(args)`` needs nothing but the
 reference's own namespace to train on the same item sequence the reference's workers would have drawn.
+``DeviceItemStreams`` / ``DeviceStreamFeeder`` are the same streams and the same rings with the generator on the device
+(csrc/irbpp_itemgen.hip): a refill is one kernel on the group's stream, and the host neither reads nor waits.
 """
 from __future__ import annotations
 
@@ -71,9 +73,10 @@ class ItemStream(object):
             pass
 
 
-def streams_for_args(args, num_envs: int, rank_offset: int = 0) -> List[ItemStream]:
+def streams_for_args(args, num_envs: int, rank_offset: int = 0, device=False):
     """The creators PackingGame.__init__ picks for training (binPhy.py:58-67), one per environment, seeded
-    ``args.seed + rank`` like envs.py:41.  ``args.dicPath`` may be the dict itself or the path of ``id2shape.pt``."""
+    ``args.seed + rank`` like envs.py:41.  ``args.dicPath`` may be the dict itself or the path of ``id2shape.pt``.
+    ``device``: False -> a list of host ``ItemStream``; True (``args.device``) or a device -> one ``DeviceItemStreams``."""
     dic = args.dicPath
     if isinstance(dic, str):
         import torch
@@ -86,6 +89,12 @@ def streams_for_args(args, num_envs: int, rank_offset: int = 0) -> List[ItemStre
     else:
         assert sample == "pose"
         groups, item_set = None, list(range(len(dic)))                      # np.arange(0, len(shapeDict))
+    if device is not False and device is not None:
+        if device is True:
+            device = args.device
+        if not isinstance(device, str) and not hasattr(device, "type"):
+            device = f"cuda:{int(device)}"
+        return DeviceItemStreams([int(args.seed) + rank_offset + i for i in range(num_envs)], groups, item_set, device=device)
     return [ItemStream(int(args.seed) + rank_offset + i, groups, item_set) for i in range(num_envs)]
 
 
@@ -159,3 +168,123 @@ class StreamFeeder(object):
                                                       C.c_void_p(t_count.data_ptr()), width, env._stream()), "irbpp_stream_write")
                 torch.cuda.current_stream(dev).synchronize()                 # the staging tensors may go now
                 self.written[rows] += count
+
+
+class DeviceItemStreams(object):
+    """``len(seeds)`` item streams over one set of lists, generated on the device: stream i equals
+    ``ItemStream(seeds[i], groups, item_set)`` item for item.  The state (624 key words, position, items delivered per
+    stream) lives in device memory; seeding runs there too, so construction uploads the seeds and the lists only."""
+
+    def __init__(self, seeds: Sequence[int], groups: Optional[Sequence[Sequence[int]]] = None,
+                 item_set: Optional[Sequence[int]] = None, device="cuda:0"):
+        import torch
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        if self.device.type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError("DeviceItemStreams needs a HIP device; the host generator is ItemStream")
+        index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda", index)
+        if groups is not None:
+            members = np.ascontiguousarray(np.concatenate([np.asarray(g, dtype=np.int32) for g in groups]))
+            offs = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int32))
+            n_groups, offs_p = len(groups), offs.ctypes.data_as(_lib.c_i32_p)
+        else:
+            members = np.ascontiguousarray(np.asarray(item_set, dtype=np.int32))
+            n_groups, offs_p = 0, None
+        if any(not 0 <= int(s) <= 2 ** 32 - 1 for s in seeds):
+            raise ValueError("Seed must be between 0 and 2**32 - 1")           # np.random.seed's own rule
+        seeds_np = np.ascontiguousarray(np.asarray([int(s) for s in seeds], dtype=np.uint32))
+        self.n = len(seeds_np)
+        self._h = C.c_void_p()
+        _lib.check(self.lib.irbpp_itemgen_dev_create(index, self.n, seeds_np.ctypes.data_as(C.POINTER(C.c_uint32)), n_groups, offs_p,
+                                                     members.ctypes.data_as(_lib.c_i32_p), len(members), self._stream(),
+                                                     C.byref(self._h)), "irbpp_itemgen_dev_create")
+
+    def __len__(self) -> int:
+        return self.n
+
+    def _stream(self, stream=None):
+        import torch
+        return C.c_void_p((stream if stream is not None else torch.cuda.current_stream(self.device)).cuda_stream)
+
+    def draw(self, count: int):
+        """The next ``count`` items of every stream: int32[n, count] on the device, in flight on the current stream."""
+        import torch
+        out = torch.empty((self.n, int(count)), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.irbpp_itemgen_dev_draw(self._h, int(count), C.c_void_p(out.data_ptr()), self._stream()),
+                   "irbpp_itemgen_dev_draw")
+        return out
+
+    def delivered(self):
+        """Items every stream has written so far (draws and refills): int64[n] on the device, current stream."""
+        import torch
+        out = torch.empty((self.n,), dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.irbpp_itemgen_dev_delivered(self._h, C.c_void_p(out.data_ptr()), self._stream()),
+                   "irbpp_itemgen_dev_delivered")
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.lib.irbpp_itemgen_dev_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceStreamFeeder(object):
+    """``StreamFeeder`` with the generator on the device: same rings, same cadence (a refill every
+    ``ring_len // (4 * bufferSize)`` ticks), same parts (group g's sub-environment is fed by streams
+    [g*per, (g+1)*per) on the group's own HIP stream) -- but a refill is ``irbpp_stream_refill``, one kernel that reads
+    the bins' cursors, draws what they have consumed and writes it into the rings, ordered with the steps on that stream.
+    Nothing is read back and nothing waits: a ring that ran dry shows as IRBPP_DEVERR_STREAM_DRY in the error word, at
+    the bin's fetch or at the refill that finds the cursor beyond what was delivered.  The environment is created over
+    ``initial``, a placeholder table of -1; ``attach`` fills the rings."""
+
+    def __init__(self, streams: DeviceItemStreams, ring_len: int = 4096, buffer_size: int = 1):
+        self.streams = streams
+        self.ring_len = int(ring_len)
+        self.K = int(buffer_size)
+        if self.ring_len < 16 * self.K:
+            raise ValueError("ring_len must be at least 16 * bufferSize")
+        self.n = len(streams)
+        self.initial = np.full((self.n, self.ring_len), -1, dtype=np.int32)
+        self.every = max(1, self.ring_len // (4 * self.K))
+        self.steps = 0
+        self.env = None
+        self.parts = []
+
+    def attach(self, env) -> None:
+        """``env``: the GpuPackingEnv (or GroupedPackingEnv) that was created with ``sequences=self.initial,
+        item_stream=1``.  The first refill happens here: nothing delivered, nothing consumed, so every ring is filled."""
+        import torch
+        assert env.num_bins == self.n
+        self.env = env
+        if hasattr(env, "groups"):                                           # (sub-environment, its first stream, its HIP stream)
+            self.parts = [(e, g * env.per, env.streams[g]) for g, e in enumerate(env.groups)]
+            cur = torch.cuda.current_stream(self.streams.device)
+            for st in env.streams:
+                st.wait_stream(cur)                                          # the streams were seeded on the current stream
+        else:
+            self.parts = [(env, 0, None)]
+        self.refill()
+
+    def tick(self, steps: int = 1) -> None:
+        """Call once per environment step (or get_action_candidates + step pair), reset or reset_specific."""
+        self.steps += steps
+        if self.steps >= self.every:
+            self.refill()
+
+    def refill(self) -> None:
+        self.steps = 0
+        for env, first, st in self.parts:
+            _lib.check(env.lib.irbpp_stream_refill(env._h, self.streams._h, first, env._stream(st)), "irbpp_stream_refill")
+
+    def delivered(self) -> np.ndarray:
+        """Items delivered per stream so far, on the host (tests and tooling: this one synchronises)."""
+        if self.env is not None and hasattr(self.env, "synchronize"):
+            self.env.synchronize()
+        return self.streams.delivered().cpu().numpy()

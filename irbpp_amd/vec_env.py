@@ -711,7 +711,7 @@ class GpuVecEnv(object):
         (GroupedPackingEnv); 0: as many as ``groups_for`` recommends for this data set and size; ``step()`` still covers all envs, and ``step_async(actions, group=g)`` /
         ``step_wait(group=g)`` let an actor loop work on one group while the others step.  (A caller that only ever calls the
         synchronous ``step()`` is best served by one group: the groups' launches are host time on its one dependent chain.)
-        ``feeder``: an ``itemgen.StreamFeeder`` for environments created with ``item_stream=1``."""
+        ``feeder``: an ``itemgen.StreamFeeder`` or ``itemgen.DeviceStreamFeeder`` for environments created with ``item_stream=1``."""
         self.num_groups = int(num_groups)
         if self.num_groups == 0:            # the library's own choice (groups_for): which overlap path does this data set take?
             probe = GpuPackingEnv(shapes, sequences[:1], 1, device=device, **{k: v for k, v in env_kw.items() if k != "item_stream"})
@@ -980,6 +980,9 @@ def make_vec_envs(args, log_dir=None, allow_early_resets=False):
       * otherwise the training-time creators of binPhy.py:60-67 (``args.dataSample`` over ``args.dicPath``), every
         environment on its own np.random stream seeded ``args.seed + rank`` exactly like envs.py:41: the items each
         environment sees are the ones the reference's worker of that rank would have drawn (itemgen.py).
+        ``args.item_feed`` (not a reference argument): absent or "host" = the streams are drawn on the host and the rings
+        refilled by ``itemgen.StreamFeeder``; "device" = the same streams drawn on the device
+        (``itemgen.DeviceStreamFeeder``: a refill is one kernel on the stepping stream, no read-back, no wait).
     """
     shapes = getattr(args, "shapes", None)
     if shapes is None:
@@ -999,8 +1002,15 @@ def make_vec_envs(args, log_dir=None, allow_early_resets=False):
             sequences[i, :len(t)] = [(-1 if v is None else int(v)) for v in t]
     if sequences is None:
         from . import itemgen
-        feeder = itemgen.StreamFeeder(itemgen.streams_for_args(args, args.num_processes),
-                                      ring_len=int(getattr(args, "item_ring", 4096)), buffer_size=args.bufferSize)
+        item_feed = getattr(args, "item_feed", "host")
+        if item_feed == "device":
+            feeder = itemgen.DeviceStreamFeeder(itemgen.streams_for_args(args, args.num_processes, device=dev),
+                                                ring_len=int(getattr(args, "item_ring", 4096)), buffer_size=args.bufferSize)
+        elif item_feed != "host":
+            raise ValueError('args.item_feed must be "host" or "device"')
+        else:
+            feeder = itemgen.StreamFeeder(itemgen.streams_for_args(args, args.num_processes),
+                                          ring_len=int(getattr(args, "item_ring", 4096)), buffer_size=args.bufferSize)
         sequences, kw["item_stream"] = feeder.initial, 1
     if getattr(args, "tuning", 0):           # (not a reference argument: irbpp_config::tuning, A/B runs and tests)
         kw["tuning"] = int(args.tuning)
