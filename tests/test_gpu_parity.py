@@ -649,7 +649,7 @@ def test_dataset_directory_with_meshes_is_rasterised_and_cached(tmp_path):
 
 def test_shot_item_rasteriser_matches_oracle_and_analytic_tables():
     """tools.shot_item (tools.py:98-135) on the GPU: boxes and polycube meshes reproduce the
-    analytic tables of the synthetic generators exactly; a slanted solid matches the numpy oracle."""
+    analytic tables of the synthetic generators exactly; a slanted solid equals the numpy oracle bit for bit."""
     from irbpp_amd import meshes
     from oracle.shot import shot_item
     # boxes (Cube dataset)
@@ -683,7 +683,7 @@ def test_shot_item_rasteriser_matches_oracle_and_analytic_tables():
         ext, tab = meshes.shot_item_gpu(vr, f, 0.01, DEV)
         ref = shot_item(vr - vr.min(0), f, 0.01)
         for got, want in zip(tab, ref):
-            np.testing.assert_allclose(got, want, rtol=0, atol=1e-12)
+            np.testing.assert_array_equal(got, want)
         assert tab[2].sum() > 20 and (tab[0] >= tab[1]).all()
 
 
