@@ -119,6 +119,9 @@ typedef struct {
 #define IRBPP_TUNE_RECT 4194304      /* the transition kernel marks the vertices of level-image components that are isolated solid rectangles
                                       * itself, as it does isolated pixels (default: the trace kernel follows them like every other border --
                                       * measured: trace -5 us, polygon -2 us, transition +6 us at 8192 BlockOut bins, profiles/r06/LOG.md s21) */
+#define IRBPP_TUNE_NO_ROT_ALIAS 8388608 /* every rotation of an item builds its own observation, also where another rotation of the item has
+                                         bit-identical footprint sizes, bottom table and ext_z_r (default: such a rotation reuses the other's
+                                         drop heights and vertex bits, irbpp_rotalias.h); identical results, for A/B runs and the parity tests */
 #define IRBPP_TUNE_NO_SPECIALISED 1024 /* the run-time builds of the transition / emit kernels even where a build with the
                                          geometry as compile-time constants exists (16 x 16 action cells, step 2 or 4, R = 2 / 4 / 8,
                                          S = 500: BASELINE.json's configs); identical results, for A/B runs and the parity tests  */

@@ -16,7 +16,8 @@
 
 #include "../../include/irbpp.h"
 #include "irbpp_device.h"
-#include "irbpp_kernels.hip"      // single translation unit: kernels + host ABI
+#include "irbpp_rotalias.h"
+#include "irbpp_kernels.hip"     // single translation unit: kernels + host ABI
 #include "irbpp_wide.hip"         // action grids of 17 .. 32 cells a side: the capacity path
 #include "irbpp_replay.hip"
 #include "irbpp_itemgen.hip"        // the item streams of irbpp_itemgen.h drawn on the device (irbpp_itemgen_dev_*, irbpp_stream_refill)
@@ -433,6 +434,28 @@ int irbpp_load_shapes(irbpp_env* env, int32_t n_shapes, const double* extents, c
                 s.bc = height_bottom[off];
             }
             if (s.nb == 0 && !s.has_out) return IRBPP_ERR_ARG;
+        }
+    }
+    // Rotations of one shape whose observation inputs are bit-identical (symmetric polycubes: a fifth of BlockOut's rotations):
+    // the later one reuses the earlier one's overlap results and vertex bits (irbpp_rotalias.h).  Identity on the
+    // capacity path and under IRBPP_TUNE_NO_ROT_ALIAS, and for every rotation that walks its cell list (generic path, the list
+    // rotations of PATH_MIXED): only the block and box loops of the overlap test skip aliased rotations -- with the skip in the list
+    // loop as well the capped generic builds went 4 to 8 bytes over their scratch budget (tests/test_kernel_asm.py).
+    {
+        const bool off = P.wide || (env->cfg.tuning & IRBPP_TUNE_NO_ROT_ALIAS) || R > 8;
+        std::vector<RotView> views((size_t)R);
+        std::vector<int32_t> alias((size_t)R);
+        for (int k = 0; k < n_shapes; ++k) {
+            for (int r = 0; r < R; ++r) {
+                const size_t i = (size_t)k * R + r;
+                views[r] = RotView{sr[i].fx, sr[i].fy, sr[i].ax, sr[i].ay, sr[i].has_out, sr[i].ext_z_r, mask_bottom + offsets[i], height_bottom + offsets[i]};
+            }
+            rot_aliases(views.data(), R, alias.data());
+            for (int r = 0; r < R; ++r) {
+                const int c = alias[r];
+                const bool skips = box || (((block_rots >> r) & 1) && ((block_rots >> c) & 1));
+                sr[(size_t)k * R + r].alias = (off || !skips) ? r : c;
+            }
         }
     }
     if (bcell.empty()) bcell.push_back(Cell{0.0, 0, 0});

@@ -47,8 +47,9 @@ struct ShapeRot {
     int32_t nb, nt;        // number of maskB==1 / maskH==1 cells
     int32_t ob, ot;        // offsets of this (shape, rot) in the bottom / top cell lists
     int32_t has_out;       // 1 iff some maskB==0 cell exists: the window max then includes (H-B)*0 = 0
-    int32_t pad;
-    int32_t nblk, oblk;    // block list (Params.block_b > 0): uniform-bottom b x b tiles of the footprint
+    int32_t alias;         // the lowest rotation of the shape with bit-identical fx, fy, ax, ay, bottom table and ext_z_r (irbpp_rotalias.h);
+                           // == own index: the rotation builds its own observation
+    int32_t nblk, oblk;   // block list (Params.block_b > 0): uniform-bottom b x b tiles of the footprint
     int32_t bx, by;        // box path (Params.box): maskB is the solid rectangle [0,bx) x [0,by) with one bottom height bc
     double bc;
     double ext_x, ext_y, ext_z;   // raw mesh.extents (prejudge, simulateHeight)
@@ -115,7 +116,8 @@ struct State {
     double* w_posz;        // [N][R*AC] posZmap of the observed item, written only where naiveMask is set (w_valid says where)
     uint32_t* w_valid;     // [N][R*16] naiveMask of the observed item as bit rows: bit Y of word r*16 + X
     uint32_t* w_vmask;     // [N][R*16] vertex bits: isolated pixels from the transition kernel, the rest from the trace kernel
-    int32_t* w_meta;       // [N][WMETA]: level images handed over, candidates handed over, np.sum(naiveMask), observed item
+    int32_t* w_meta;       // [N][WMETA]: level images handed over, candidates handed over, np.sum(naiveMask), observed item, heavy flag,
+                           // [5] ShapeRot::alias of the item's rotation r in bits 4r .. 4r+3 (whose w_vmask rows the emit kernel reads for r)
     uint16_t* w_img;       // [N][wimg][16] level images: 16 row words (bit x of word y = pixel (x, y))
     uint8_t* w_imgrot;     // [N][wimg] rotation of each level image
     uint2* w_cand;         // [NXCD][seg_cap] flat lists of the launch's candidate starts, in arrival order:

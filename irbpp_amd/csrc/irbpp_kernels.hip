@@ -383,6 +383,20 @@ __device__ inline Lds carve_lds(unsigned char* smem, const Params& P) {
     return L;
 }
 
+// Rotation aliases of the observed item, from the ShapeRots staged in L.sr: ShapeRot::alias of rotation r in bits 4r .. 4r+3
+// (identity where there is no item).  A rotation whose alias is a lower rotation has that rotation's observation inputs bit for
+// bit: the overlap test copies its results and hands no level images over, the emit side reads the alias's vertex bits.
+constexpr uint32_t ALIAS_IDENTITY = 0x76543210u;
+__device__ __forceinline__ uint32_t alias_map(const Lds& L, int R, int item) {
+    if (item < 0) return ALIAS_IDENTITY;
+    const ShapeRot* sa = (const ShapeRot*)L.sr;
+    uint32_t m = ALIAS_IDENTITY;
+#pragma unroll
+    for (int r = 1; r < 8; ++r)
+        if (r < R) m = (m & ~(15u << (4 * r))) | ((uint32_t)sa[r].alias << (4 * r));
+    return m;
+}
+
 #endif  // IRBPP_PASS == 1
 // ---------------------------------------------------------------------------------------
 // cvTools.getConvexHullActions on the grids in LDS: L.posz = posZValid [R][AC] (1e3 where
@@ -956,6 +970,15 @@ __device__ inline int overlap_test(const Params& P, const Tables& T, const State
 
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int my_valid = 0;
+    // Rotations with the observation inputs of a lower rotation (alias_map): same drop heights, same naiveMask on every heightmap.
+    // They take the canonical rotation's z and validity instead of walking their footprint again, still write their own posZmap /
+    // naiveMask rows and count in np.sum(naiveMask), and get no level codes: no images, no border starts, no vertex bits of their own.
+    // (ShapeRot::alias is read from the ShapeRots staged in LDS where it is needed: a register that lives through the loops costs
+    // the capped builds a spill.  Without an item nothing is valid and nothing gets a task, whatever the stale words say.)
+#define IRBPP_ALIAS_OF(r) __builtin_amdgcn_readfirstlane(((const ShapeRot*)srw)[r].alias)
+#define IRBPP_ALIAS_COPY(r, al)                                                                                         \
+    _Pragma("unroll") for (int c_ = 0; c_ < 7; ++c_)                                                                    \
+        if (c_ < (r) && (al) == c_) { zs[r] = zs[c_]; vs[r] = vs[c_]; }
     if (use_block || use_box) {
     // ---- one action cell per thread, all rotations: block path (footprint = list of uniform b x b blocks over the
     // block-max grid) or box path (footprint = one solid box: separable rectangle maximum) ---------------------------
@@ -978,6 +1001,7 @@ __device__ inline int overlap_test(const Params& P, const Tables& T, const State
             vs[r] = false;
             if (r >= R || item < 0) continue;
             const ShapeRot* sp = (const ShapeRot*)srw + r;
+            if (const int al = IRBPP_ALIAS_OF(r); al != r) { IRBPP_ALIAS_COPY(r, al) continue; }      // (block-uniform: the barriers below are skipped by all)
             const int s_ax = __builtin_amdgcn_readfirstlane(sp->ax), s_ay = __builtin_amdgcn_readfirstlane(sp->ay);
             const int bx = __builtin_amdgcn_readfirstlane(sp->bx), by = __builtin_amdgcn_readfirstlane(sp->by);
             const int has_out = __builtin_amdgcn_readfirstlane(sp->has_out);
@@ -1016,6 +1040,7 @@ __device__ inline int overlap_test(const Params& P, const Tables& T, const State
         zs[r] = 1e3;
         vs[r] = false;
         if (r >= R || !((brots >> r) & 1u)) continue;
+        if (const int al = IRBPP_ALIAS_OF(r); al != r) { IRBPP_ALIAS_COPY(r, al) continue; }
         const ShapeRot* sp = (const ShapeRot*)srw + r;
         const int s_ax = __builtin_amdgcn_readfirstlane(sp->ax), s_ay = __builtin_amdgcn_readfirstlane(sp->ay);
         const int has_out = __builtin_amdgcn_readfirstlane(sp->has_out);
@@ -1064,7 +1089,9 @@ __device__ inline int overlap_test(const Params& P, const Tables& T, const State
         const int s_ax = __builtin_amdgcn_readfirstlane(sp->ax), s_ay = __builtin_amdgcn_readfirstlane(sp->ay);
         const int has_out = __builtin_amdgcn_readfirstlane(sp->has_out);
         const double ext_z_r = sp->ext_z_r;
-        const int ncell = ((brots >> r) & 1u) ? ncell_next : 0, off0 = off_next;     // (a list rotation has no blocks: nblk = 0 anyway)
+        const int al = IRBPP_ALIAS_OF(r);
+        const bool own = al == r;
+        const int ncell = (((brots >> r) & 1u) && own) ? ncell_next : 0, off0 = off_next;     // (a list rotation has no blocks: nblk = 0 anyway)
         Cell c = pre;
         if (r + 1 < R) {                                     // issue the next rotation's first chunk now
             const ShapeRot* sn = sp + 1;
@@ -1113,7 +1140,9 @@ __device__ inline int overlap_test(const Params& P, const Tables& T, const State
                 }
             }
         }
-        if (in_range && ((brots >> r) & 1u)) {
+        if (!own) {
+            IRBPP_ALIAS_COPY(r, al)
+        } else if (in_range && ((brots >> r) & 1u)) {
             zs[r] = m;
             vs[r] = round6_scaled(m + ext_z_r - P.bin_z) <= 0.0;     // np.round(.,6) <= 0 (space.py:120)
         }
@@ -1139,11 +1168,13 @@ __device__ inline int overlap_test(const Params& P, const Tables& T, const State
             int code = 255;
             if (valid) {
                 if (!debug_out) zdst[r * AC + cell] = z;                // (irbpp_possible_position leaves the last observation's hand-over alone: the next step reads its drop height there)
+                if (IRBPP_ALIAS_OF(r) == r) {                           // (an aliased rotation has no level images)
                 const int li = np_floor_divide_int(z, P.res_z, P.inv_res_z);   // cvTools.py:78
                 if (li != -1) {                                        // level -1 is skipped (cvTools.py:84)
                     const int idx = li + 32;
                     if (idx < 0 || idx > 63) raise_error(S, IRBPP_DEVERR_LEVEL_RANGE);
                     else code = idx;
+                }
                 }
                 ++my_valid;
                 L.lev[r * AC + cell] = (uint8_t)code;
@@ -1160,7 +1191,7 @@ __device__ inline int overlap_test(const Params& P, const Tables& T, const State
     // be serialised by the LDS lane by lane)
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
-        if (r >= R || (!use_box && !((brots >> r) & 1u))) continue;
+        if (r >= R || (!use_box && !((brots >> r) & 1u)) || IRBPP_ALIAS_OF(r) != r) continue;
         const int code = level_code[r];
         unsigned long long todo = __ballot(code != 255), bits = 0ull;
         while (todo) {
@@ -1341,11 +1372,13 @@ __device__ inline int overlap_test(const Params& P, const Tables& T, const State
             }
         }
     }
+#undef IRBPP_ALIAS_COPY
+#undef IRBPP_ALIAS_OF
     return block_sum_int(my_valid, L.redi);                  // np.sum(naiveMask) for prejudge
 }
 
 __device__ inline void emit_observation(const Params& P, const State& S, const StepIO& io, const Lds& L, int b, int item,
-                                        int nvalid, float* obs, const double* zsrc, const uint32_t* gvalid);
+                                        int nvalid, float* obs, const double* zsrc, const uint32_t* gvalid, uint32_t amap);
 template <int IPT>
 __device__ inline void split_handover(const Params& P, const State& S, const Lds& L, int b, int slot, int item, int nvalid);
 
@@ -1393,7 +1426,8 @@ __device__ inline void observe_location(const Params& P, const Tables& T, const 
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         Lds Le = L;
         Le.img = (uint16_t*)chain_lds;               // radix counters / sort keys of a > S selection: behind the transition kernel's own carve-up
-        ::irbpp::emit_observation(P, S, io, Le, b, item, nvalid, obs, S.w_posz + (size_t)b * R * AC, S.w_valid + (size_t)b * R * 16);
+        ::irbpp::emit_observation(P, S, io, Le, b, item, nvalid, obs, S.w_posz + (size_t)b * R * AC, S.w_valid + (size_t)b * R * 16,
+                                  ::irbpp::alias_map(L, R, item));
         return;
     }
     // the trace and emit kernels take it from here
@@ -1553,7 +1587,9 @@ __device__ inline void select_smallest(const Params& P, const Lds& L, const doub
 #define IRBPP_EMIT_STAMP(k) do {} while (0)
 #endif
 __device__ inline void emit_observation(const Params& P, const State& S, const StepIO& io, const Lds& L, int b, int item,
-                                        int nvalid, float* obs, const double* zsrc, const uint32_t* gvalid) {
+                                        int nvalid, float* obs, const double* zsrc, const uint32_t* gvalid, uint32_t amap) {
+    // amap: rotation r lists the vertex bits of rotation (amap >> 4r) & 15, a lower rotation with bit-identical observation inputs
+    // (alias_map; its own rows are empty) -- the keys carry r itself, and posZValid / naiveMask are read at r's own rows
     const int tid = threadIdx.x;
     const int R = P.R, AC = P.AC, Ax = P.Ax, Ay = P.Ay;
     const int X = fdiv(tid, Ay, P.mg_ay), Y = tid - X * Ay;
@@ -1577,8 +1613,9 @@ __device__ inline void emit_observation(const Params& P, const State& S, const S
             const int r = r0 + (lane >> 4);
             uint32_t col = 0u;
             if (r < R && cx < Ay) {
+                const uint32_t* const vrow = L.vmask + ((amap >> (4 * r)) & 15u) * 16;
 #pragma unroll
-                for (int cy = 0; cy < 16; ++cy) col |= ((L.vmask[r * 16 + cy] >> cx) & 1u) << cy;
+                for (int cy = 0; cy < 16; ++cy) col |= ((vrow[cy] >> cx) & 1u) << cy;
                 col &= (1u << Ax) - 1u;
             }
             const int cnt = __popc(col), incl = wave_inclusive_sum(cnt);
@@ -1799,6 +1836,7 @@ __device__ inline void split_handover(const Params& P, const State& S, const Lds
         m[1] = ncand;
         m[2] = nvalid;
         m[3] = item;
+        m[5] = (int32_t)alias_map(L, P.R, item);     // whose vertex-bit rows the emit kernel reads for each rotation
         // A bin with many border starts (speckled level images) is a bin whose observation is expensive: more than S
         // candidates mean a radix select and a sort, five times the time of an ordinary bin, and the emit kernel lasts as
         // long as the last of them.  Such bins enter a list that the emit kernel serves FIRST (its leading workgroups); the
@@ -1877,9 +1915,10 @@ __device__ __forceinline__ void emit_body(const Params& P_run, const Tables& T, 
 #pragma unroll 1
     for (int i = tid; i < P.R * 16; i += BLOCK) L.vmask[i] = gv[i];
     const int nvalid = S.w_meta[(size_t)b * WMETA + 2], item = S.w_meta[(size_t)b * WMETA + 3];
+    const uint32_t amap = (uint32_t)S.w_meta[(size_t)b * WMETA + 5];
     __syncthreads();
     stamp(io, b, 3);
-    emit_observation(P, S, io, L, b, item, nvalid, obs, S.w_posz + (size_t)b * P.R * P.AC, S.w_valid + (size_t)b * P.R * 16);
+    emit_observation(P, S, io, L, b, item, nvalid, obs, S.w_posz + (size_t)b * P.R * P.AC, S.w_valid + (size_t)b * P.R * 16, amap);
     IRBPP_EMIT_STAMP(14);
 }
 #define IRBPP_EMIT_KERNEL(NAME, HF, SPEC)                                                                                \
@@ -1931,6 +1970,7 @@ __device__ __forceinline__ void emit_wave_body(const Params& P_run, const Tables
         const uint32_t* gv = S.w_vmask + (size_t)b * R * 16;
         for (int i = lane; i < R * 16; i += 64) vm[i] = gv[i];
         const int nvalid = S.w_meta[(size_t)b * WMETA + 2], item = S.w_meta[(size_t)b * WMETA + 3];
+        const uint32_t amap = (uint32_t)S.w_meta[(size_t)b * WMETA + 5];      // (alias_map: whose vertex bits a rotation lists)
         const int prev_rows = io.obs_rows != nullptr ? io.obs_rows[b] : -1;
         float* const obs = io.obs + (size_t)(some ? slot : b) * io.obs_stride;
         const double* const zsrc = S.w_posz + (size_t)b * R * AC;
@@ -1943,8 +1983,9 @@ __device__ __forceinline__ void emit_wave_body(const Params& P_run, const Tables
         auto column = [&](int r) {                                     // my column of rotation r: bit cy = vertex at (row cy, col cx)
             uint32_t col = 0u;
             if (r < R && cx < Ay) {
+                const uint32_t* const vrow = vm + ((amap >> (4 * r)) & 15u) * 16;
 #pragma unroll
-                for (int cy = 0; cy < 16; ++cy) col |= ((vm[r * 16 + cy] >> cx) & 1u) << cy;
+                for (int cy = 0; cy < 16; ++cy) col |= ((vrow[cy] >> cx) & 1u) << cy;
                 col &= (1u << Ax) - 1u;
             }
             return col;
@@ -2044,9 +2085,10 @@ __device__ __forceinline__ void emit_wave_body(const Params& P_run, const Tables
 #pragma unroll 1
         for (int i = tid; i < R * 16; i += BLOCK) L.vmask[i] = gv[i];
         const int nvalid = S.w_meta[(size_t)bw * WMETA + 2], item = S.w_meta[(size_t)bw * WMETA + 3];
+        const uint32_t amap_w = (uint32_t)S.w_meta[(size_t)bw * WMETA + 5];
         __syncthreads();
         stamp(io, bw, 3);
-        emit_observation(P, S, io, L, bw, item, nvalid, obs, S.w_posz + (size_t)bw * R * AC, S.w_valid + (size_t)bw * R * 16);
+        emit_observation(P, S, io, L, bw, item, nvalid, obs, S.w_posz + (size_t)bw * R * AC, S.w_valid + (size_t)bw * R * 16, amap_w);
     }
 }
 #define IRBPP_EMIT_WAVE_KERNEL(NAME, SPEC)                                                                                  \
