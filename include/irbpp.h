@@ -471,6 +471,33 @@ int irbpp_replay_append(const irbpp_replay_store* store, const float* state_dev,
  * 0x7fffffff never occurs: with no valid candidate every q is -inf and index 0 wins, like torch.argmax). */
 int irbpp_masked_argmax(const float* q_dev, int32_t q_stride, const float* obs_dev, int32_t obs_stride, int32_t selected,
                         int32_t n_env, int64_t* action_dev, void* stream);
+/* replaces: all of Agent.act after the network (agent.py:51-58): (q_map * support).sum(2), the mask, argmax(1) -- one
+ * launch that reads the probabilities once.  p_dev float32 [n_env][s_rows][atoms], atoms contiguous, rows row_stride and
+ * envs env_stride floats apart (slices of wider tensors work); support_dev float32[atoms], the caller's own
+ * torch.linspace(Vmin, Vmax, atoms), never recomputed.  A row's value is the float32 sum, left to right over
+ * a = 0..atoms-1, of fl32(p[a] * support[a]), multiply and add separate: reproducible bit for bit.  obs_dev / obs_stride
+ * as in irbpp_masked_argmax: a row whose obs[e][5*i+4] == 0 counts as -inf; NULL = no mask (orderDQN.act(state, None),
+ * trainer.py:266).  action_dev int64[n_env]: the first maximum; index 0 if every row is masked or -inf.  q_out_dev (may
+ * be NULL) float32 rows q_stride floats apart: the unmasked values (evaluate_q, agent.py:135-137; logging).
+ * IRBPP_ERR_ARG unless 2 <= atoms <= 128, 1 <= s_rows <= 1024, n_env >= 1, row_stride >= atoms,
+ * env_stride >= (s_rows-1)*row_stride + atoms, obs_stride >= 5*s_rows, q_stride >= s_rows.  NaN inputs are out of scope. */
+int irbpp_categorical_act(const float* p_dev, int64_t env_stride, int64_t row_stride, const float* support_dev, int32_t atoms,
+                          const float* obs_dev, int32_t obs_stride, int32_t s_rows, int32_t n_env, int64_t* action_dev,
+                          float* q_out_dev, int64_t q_stride, void* stream);
+/* replaces: Agent.learn between the two network calls and the loss (agent.py:88-115), one wave per sample, no atomics:
+ * a_star[b] = argmax over rows of the same defined expected value of p_online (unmasked, agent.py:92);
+ * pns_a = p_target[b][a_star[b]] (:97); Tz = returns + (nonterminals * gamma_n) * support clamped to [v_min, v_max]
+ * (:100-101); b = (Tz - v_min) / delta_z with an IEEE division; l = floor(b), u = ceil(b) and the two l == u fix-ups in
+ * the reference's order (:104-109); m[b][j] = the float32 sum of the l == j contributions pns_a[i] * (u_i - b_i) in
+ * ascending i, continued with the u == j contributions pns_a[i] * (b_i - l_i) in ascending i -- the order of the two
+ * sequential index_add_ calls (:114-115), so m is the same from run to run.  p_online_dev / p_target_dev float32
+ * [batch][s_rows][atoms] strided as in irbpp_categorical_act; returns_dev, nonterminals_dev float32[batch]; gamma_n the
+ * caller's discount ** n as float32; m_dev float32[batch][atoms]; a_star_dev int64[batch].  Same limits as
+ * irbpp_categorical_act, and batch >= 1, v_max > v_min, delta_z > 0. */
+int irbpp_categorical_target(const float* p_online_dev, int64_t online_env_stride, int64_t online_row_stride,
+                             const float* p_target_dev, int64_t target_env_stride, int64_t target_row_stride, const float* returns_dev,
+                             const float* nonterminals_dev, const float* support_dev, int32_t atoms, int32_t s_rows, int32_t batch,
+                             float gamma_n, float v_min, float v_max, float delta_z, float* m_dev, int64_t* a_star_dev, void* stream);
 
 /* Tooling: when cycles_dev != NULL every later transition launch stores, per bin, one row
  * int64[num_bins][16]: shader-clock stamps 0 start, 1 action applied, 2 overlap test done,

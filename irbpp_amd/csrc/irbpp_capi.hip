@@ -21,6 +21,7 @@
 #include "irbpp_wide.hip"         // action grids of 17 .. 32 cells a side: the capacity path
 #include "irbpp_replay.hip"
 #include "irbpp_itemgen.hip"        // the item streams of irbpp_itemgen.h drawn on the device (irbpp_itemgen_dev_*, irbpp_stream_refill)
+#include "irbpp_c51.hip"            // the distributional head around the network (irbpp_categorical_act, irbpp_categorical_target)
 #include "irbpp_metrics.hip"        // the trainer's episode metrics (irbpp_set_episode_window)
 #include "irbpp_itemgen.h"
 
@@ -1245,6 +1246,38 @@ int irbpp_masked_argmax(const float* q_dev, int32_t q_stride, const float* obs_d
         return IRBPP_ERR_ARG;
     hipLaunchKernelGGL(irbpp_masked_argmax_kernel, dim3((n_env + 3) / 4), dim3(256), 0, (hipStream_t)stream, q_dev, q_stride,
                        obs_dev, obs_stride, selected, n_env, action_dev);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+static bool c51_block_ok(const float* p, int64_t env_stride, int64_t row_stride, int32_t atoms, int32_t s_rows) {
+    return p && atoms >= 2 && atoms <= C51_MAX_ATOMS && s_rows >= 1 && s_rows <= C51_MAX_ROWS && row_stride >= atoms &&
+           env_stride >= (int64_t)(s_rows - 1) * row_stride + atoms;
+}
+
+int irbpp_categorical_act(const float* p_dev, int64_t env_stride, int64_t row_stride, const float* support_dev, int32_t atoms,
+                          const float* obs_dev, int32_t obs_stride, int32_t s_rows, int32_t n_env, int64_t* action_dev,
+                          float* q_out_dev, int64_t q_stride, void* stream) {
+    if (!c51_block_ok(p_dev, env_stride, row_stride, atoms, s_rows) || !support_dev || !action_dev || n_env < 1 ||
+        (obs_dev && obs_stride < 5 * s_rows) || (q_out_dev && q_stride < s_rows))
+        return IRBPP_ERR_ARG;
+    hipLaunchKernelGGL(irbpp_c51_act_kernel, dim3(n_env), dim3(64), (size_t)64 * (atoms | 1) * sizeof(float), (hipStream_t)stream,
+                       p_dev, (long long)env_stride, (long long)row_stride, support_dev, atoms, obs_dev, obs_stride, s_rows,
+                       action_dev, q_out_dev, (long long)q_stride);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+int irbpp_categorical_target(const float* p_online_dev, int64_t online_env_stride, int64_t online_row_stride,
+                             const float* p_target_dev, int64_t target_env_stride, int64_t target_row_stride, const float* returns_dev,
+                             const float* nonterminals_dev, const float* support_dev, int32_t atoms, int32_t s_rows, int32_t batch,
+                             float gamma_n, float v_min, float v_max, float delta_z, float* m_dev, int64_t* a_star_dev, void* stream) {
+    if (!c51_block_ok(p_online_dev, online_env_stride, online_row_stride, atoms, s_rows) ||
+        !c51_block_ok(p_target_dev, target_env_stride, target_row_stride, atoms, s_rows) || !returns_dev || !nonterminals_dev ||
+        !support_dev || !m_dev || !a_star_dev || batch < 1 || !(v_max > v_min) || !(delta_z > 0))
+        return IRBPP_ERR_ARG;
+    hipLaunchKernelGGL(irbpp_c51_target_kernel, dim3(batch), dim3(64), (size_t)64 * (atoms | 1) * sizeof(float),
+                       (hipStream_t)stream, p_online_dev, (long long)online_env_stride, (long long)online_row_stride, p_target_dev,
+                       (long long)target_env_stride, (long long)target_row_stride, returns_dev, nonterminals_dev, support_dev,
+                       atoms, s_rows, gamma_n, v_min, v_max, delta_z, m_dev, a_star_dev);
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
 }
 

@@ -358,6 +358,111 @@ def masked_greedy_action(q: torch.Tensor, state: torch.Tensor, selected_action: 
     return out
 
 
+# Which form the two distributional-head wrappers below take on a HIP device when the caller does not say (use_hip=None).
+# The torch lines, until tools/c51_head_rates.py has shown on an MI355X that the kernels are not slower than them at 4096
+# environments ("The distributional head"): use_hip=True asks for the kernels.
+C51_HIP_DEFAULT = False
+
+
+def _c51_lib(t: torch.Tensor, use_hip: Optional[bool]):
+    lib = _hip_lib(t.device)
+    if use_hip and lib is None:
+        raise RuntimeError("use_hip=True needs a HIP device")
+    return lib if (C51_HIP_DEFAULT if use_hip is None else use_hip) else None
+
+
+def _c51_block(p: torch.Tensor) -> torch.Tensor:
+    """float32 [N, S, atoms] with the atoms contiguous, whatever the row and env strides (slices pass as they are)."""
+    if p.dim() != 3:
+        raise ValueError("probabilities must be [N, S, atoms]")
+    p = p.to(torch.float32)
+    ok = p.stride(2) == 1 and p.stride(1) >= p.shape[2] and p.stride(0) >= (p.shape[1] - 1) * p.stride(1) + p.shape[2]
+    return p if ok else p.contiguous()
+
+
+def distributional_greedy_action(p: torch.Tensor, support: torch.Tensor, state: Optional[torch.Tensor] = None,
+                                 selected_action: Optional[int] = None, q_out: Optional[torch.Tensor] = None, *,
+                                 use_hip: Optional[bool] = None) -> torch.Tensor:
+    """All of Agent.act after the network (agent.py:51-58): ``(p * support).sum(2)``, ``-inf`` where the observation's
+    validity flag is 0 (``state=None``: no mask, as orderDQN.act(state, None) at trainer.py:266), ``argmax(1)`` -> int64[N].
+    ``p`` is the network's [N, S, atoms] probabilities, ``support`` the caller's ``torch.linspace(Vmin, Vmax, atoms)``;
+    ``q_out`` (optional float32 [N, S]) receives the unmasked expected values (evaluate_q, logging).  With ``use_hip=True``
+    (a HIP device; ``None`` takes C51_HIP_DEFAULT) one kernel reads ``p`` once and sums each row's atoms left to right in
+    float32 (irbpp_categorical_act: reproducible bit for bit); otherwise, and on the CPU, the reference's torch lines run."""
+    N, S, atoms = p.shape
+    if selected_action is not None and int(selected_action) != S:
+        raise ValueError(f"selected_action {selected_action} != {S} candidate rows")
+    lib = _c51_lib(p, use_hip)
+    if lib is None:
+        q = (p * support).sum(2)
+        if q_out is not None:
+            q_out.copy_(q)
+        if state is not None:
+            q[(1 - mask_from_state(state, S)).bool()] = float("-inf")
+        return q.argmax(1)
+    from . import _lib
+    p = _c51_block(p)
+    support = support.to(device=p.device, dtype=torch.float32).contiguous()
+    obs_stride = 0
+    if state is not None:
+        state = state.to(torch.float32)
+        if state.stride(1) != 1:
+            state = state.contiguous()
+        obs_stride = state.stride(0)
+    q_stride = 0
+    if q_out is not None:
+        if q_out.dtype != torch.float32 or q_out.device != p.device or tuple(q_out.shape) != (N, S) or q_out.stride(1) != 1:
+            raise ValueError("q_out must be a float32 [N, S] tensor on p's device with contiguous rows")
+        q_stride = q_out.stride(0)
+    out = torch.empty((N,), dtype=torch.int64, device=p.device)
+    _lib.check(lib.irbpp_categorical_act(_p(p), p.stride(0), p.stride(1), _p(support), atoms, _p(state), obs_stride, S, N, _p(out),
+                                         _p(q_out), q_stride, _stream(p.device)), "irbpp_categorical_act")
+    return out
+
+
+def c51_target(p_online: torch.Tensor, p_target: torch.Tensor, returns: torch.Tensor, nonterminals: torch.Tensor,
+               support: torch.Tensor, gamma_n: float, v_min: float, v_max: float, *,
+               use_hip: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Agent.learn between the two forwards and the loss (agent.py:90-115): the double-Q selection
+    ``a_star = (support * p_online).sum(2).argmax(1)``, ``pns_a = p_target[range(B), a_star]`` and the projection of
+    ``Tz = returns + nonterminals * gamma_n * support`` onto the support -> (m float32 [B, atoms], a_star int64 [B]).
+    ``gamma_n`` is ``discount ** n``.  With ``use_hip=True`` (a HIP device; ``None`` takes C51_HIP_DEFAULT) one kernel does it
+    without atomics (irbpp_categorical_target: ``m`` is the same from run to run, which torch's index_add_ on the GPU is
+    not); otherwise, and on the CPU, the reference's torch lines run."""
+    B, S, atoms = p_online.shape
+    if tuple(p_target.shape) != (B, S, atoms):
+        raise ValueError("p_online and p_target must have the same [B, S, atoms] shape")
+    delta_z = (v_max - v_min) / (atoms - 1)
+    returns, nonterminals = returns.reshape(B), nonterminals.reshape(B)
+    lib = _c51_lib(p_online, use_hip)
+    if lib is None:
+        a_star = (support.expand_as(p_online) * p_online).sum(2).argmax(1)
+        pns_a = p_target[torch.arange(B, device=p_target.device), a_star]
+        Tz = returns.unsqueeze(1) + nonterminals.unsqueeze(1) * gamma_n * support.unsqueeze(0)
+        Tz = Tz.clamp(min=v_min, max=v_max)
+        b = (Tz - v_min) / delta_z
+        l, u = b.floor().to(torch.int64), b.ceil().to(torch.int64)
+        l[(u > 0) * (l == u)] -= 1
+        u[(l < (atoms - 1)) * (l == u)] += 1
+        m = p_target.new_zeros(B, atoms)
+        offset = (torch.arange(B, device=m.device) * atoms).unsqueeze(1).expand(B, atoms)
+        m.view(-1).index_add_(0, (l + offset).view(-1), (pns_a * (u.float() - b)).view(-1))
+        m.view(-1).index_add_(0, (u + offset).view(-1), (pns_a * (b - l.float())).view(-1))
+        return m, a_star
+    from . import _lib
+    dev = p_online.device
+    p_online, p_target = _c51_block(p_online), _c51_block(p_target)
+    f32 = lambda x: x.to(device=dev, dtype=torch.float32).contiguous()      # noqa: E731
+    returns, nonterminals, support = f32(returns), f32(nonterminals), f32(support)
+    m = torch.empty((B, atoms), dtype=torch.float32, device=dev)
+    a_star = torch.empty((B,), dtype=torch.int64, device=dev)
+    _lib.check(lib.irbpp_categorical_target(_p(p_online), p_online.stride(0), p_online.stride(1), _p(p_target), p_target.stride(0),
+                                            p_target.stride(1), _p(returns), _p(nonterminals), _p(support), atoms, S, B, float(gamma_n),
+                                            float(v_min), float(v_max), float(delta_z), _p(m), _p(a_star), _stream(dev)),
+               "irbpp_categorical_target")
+    return m, a_star
+
+
 def actor_step(envs, policy, memory: VectorReplayMemory, state: torch.Tensor, reward_clip: float = 0.0):
     """One iteration of the trainer's acting loop (trainer.py:160-186) without per-env Python:
     mask -> policy -> envs.step -> clip -> append.  ``envs`` is a GpuPackingEnv (device-tensor
