@@ -498,6 +498,31 @@ int irbpp_categorical_target(const float* p_online_dev, int64_t online_env_strid
                              const float* p_target_dev, int64_t target_env_stride, int64_t target_row_stride, const float* returns_dev,
                              const float* nonterminals_dev, const float* support_dev, int32_t atoms, int32_t s_rows, int32_t batch,
                              float gamma_n, float v_min, float v_max, float delta_z, float* m_dev, int64_t* a_star_dev, void* stream);
+/* replaces: the end of DQNBPP.forward (model.py:395-400: v + a - a.mean(1), softmax over the atoms) and all of Agent.act after
+ * it (agent.py:51-58) in one launch from the network's logits: the [n_env][s_rows][atoms] probabilities never reach memory
+ * unless p_out_dev asks for them.  v_dev float32 [n_env][atoms], rows v_stride floats apart; a_dev float32
+ * [n_env][s_rows][atoms] strided as p_dev of irbpp_categorical_act; support, obs, action, q_out as there.  p_out_dev (may be
+ * NULL) float32 [n_env][s_rows][atoms], contiguous.  The float32 arithmetic is defined (csrc/irbpp_dueling.hip: 16 interleaved
+ * partial sums per column for the mean, x = (v + a) - mean, a maximum-subtracted softmax with the library's own exponential,
+ * exactly 0 below -80, the denominator summed in ascending atoms, IEEE divisions, the expected value of
+ * irbpp_categorical_act) and reproducible bit for bit whatever n_env, the strides and the block's size.  Logits must be
+ * finite: a NaN or an infinity gives unspecified q_out / p_out values, the action is still a row index in [0, s_rows) and
+ * nothing is accessed out of range.  IRBPP_ERR_ARG unless 2 <= atoms <= 128, 1 <= s_rows <= 1024, n_env >= 1,
+ * v_stride >= atoms, row_stride >= atoms, env_stride >= (s_rows-1)*row_stride + atoms, obs_stride >= 5*s_rows,
+ * q_stride >= s_rows. */
+int irbpp_dueling_act(const float* v_dev, int64_t v_stride, const float* a_dev, int64_t env_stride, int64_t row_stride,
+                      const float* support_dev, int32_t atoms, const float* obs_dev, int32_t obs_stride, int32_t s_rows,
+                      int32_t n_env, int64_t* action_dev, float* q_out_dev, int64_t q_stride, float* p_out_dev, void* stream);
+/* replaces: Agent.learn's no_grad block (agent.py:90-115) from the logits of the two networks: a_star from the online (v, a) by
+ * the arithmetic of irbpp_dueling_act, unmasked; pns_a = row a_star of the target net's softmax by the same arithmetic (the
+ * target block's mean and that one row); then the projection of irbpp_categorical_target operation for operation, no
+ * atomics.  Blocks strided as in irbpp_dueling_act, the other arguments and limits as in irbpp_categorical_target.  The same
+ * rule for non-finite logits: unspecified m, a_star in [0, s_rows). */
+int irbpp_dueling_target(const float* v_online_dev, int64_t v_online_stride, const float* a_online_dev, int64_t online_env_stride,
+                         int64_t online_row_stride, const float* v_target_dev, int64_t v_target_stride, const float* a_target_dev,
+                         int64_t target_env_stride, int64_t target_row_stride, const float* returns_dev,
+                         const float* nonterminals_dev, const float* support_dev, int32_t atoms, int32_t s_rows, int32_t batch,
+                         float gamma_n, float v_min, float v_max, float delta_z, float* m_dev, int64_t* a_star_dev, void* stream);
 
 /* Tooling: when cycles_dev != NULL every later transition launch stores, per bin, one row
  * int64[num_bins][16]: shader-clock stamps 0 start, 1 action applied, 2 overlap test done,

@@ -22,6 +22,7 @@
 #include "irbpp_replay.hip"
 #include "irbpp_itemgen.hip"        // the item streams of irbpp_itemgen.h drawn on the device (irbpp_itemgen_dev_*, irbpp_stream_refill)
 #include "irbpp_c51.hip"            // the distributional head around the network (irbpp_categorical_act, irbpp_categorical_target)
+#include "irbpp_dueling.hip"        // the same from the network's logits: dueling combine + softmax fused in (irbpp_dueling_act, irbpp_dueling_target)
 #include "irbpp_metrics.hip"        // the trainer's episode metrics (irbpp_set_episode_window)
 #include "irbpp_itemgen.h"
 
@@ -1278,6 +1279,53 @@ int irbpp_categorical_target(const float* p_online_dev, int64_t online_env_strid
                        (hipStream_t)stream, p_online_dev, (long long)online_env_stride, (long long)online_row_stride, p_target_dev,
                        (long long)target_env_stride, (long long)target_row_stride, returns_dev, nonterminals_dev, support_dev,
                        atoms, s_rows, gamma_n, v_min, v_max, delta_z, m_dev, a_star_dev);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+static bool dueling_block_ok(const float* v, int64_t v_stride, const float* a, int64_t env_stride, int64_t row_stride, int32_t atoms,
+                             int32_t s_rows) {
+    return v && a && atoms >= 2 && atoms <= DUELING_MAX_ATOMS && s_rows >= 1 && s_rows <= DUELING_MAX_ROWS && v_stride >= atoms &&
+           row_stride >= atoms && env_stride >= (int64_t)(s_rows - 1) * row_stride + atoms;
+}
+
+// dynamic LDS of a dueling launch; above 64 KB the kernel is told (on the current device) that it may be given that much
+static bool dueling_lds(const void* kernel, int32_t atoms, int32_t s_rows, size_t* bytes) {
+    *bytes = (size_t)dueling_tile_rows(s_rows, atoms) * (atoms | 1) * sizeof(float);
+    return *bytes <= 64 * 1024 ||
+           hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DUELING_TILE_BYTES) == hipSuccess;
+}
+
+int irbpp_dueling_act(const float* v_dev, int64_t v_stride, const float* a_dev, int64_t env_stride, int64_t row_stride,
+                      const float* support_dev, int32_t atoms, const float* obs_dev, int32_t obs_stride, int32_t s_rows,
+                      int32_t n_env, int64_t* action_dev, float* q_out_dev, int64_t q_stride, float* p_out_dev, void* stream) {
+    if (!dueling_block_ok(v_dev, v_stride, a_dev, env_stride, row_stride, atoms, s_rows) || !support_dev || !action_dev ||
+        n_env < 1 || (obs_dev && obs_stride < 5 * s_rows) || (q_out_dev && q_stride < s_rows))
+        return IRBPP_ERR_ARG;
+    size_t lds;
+    if (!dueling_lds((const void*)irbpp_dueling_act_kernel, atoms, s_rows, &lds)) return IRBPP_ERR_HIP;
+    hipLaunchKernelGGL(irbpp_dueling_act_kernel, dim3(n_env), dim3(DUELING_THREADS), lds, (hipStream_t)stream, v_dev,
+                       (long long)v_stride, a_dev, (long long)env_stride, (long long)row_stride, support_dev, atoms, obs_dev,
+                       obs_stride, s_rows, action_dev, q_out_dev, (long long)q_stride, p_out_dev);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+int irbpp_dueling_target(const float* v_online_dev, int64_t v_online_stride, const float* a_online_dev, int64_t online_env_stride,
+                         int64_t online_row_stride, const float* v_target_dev, int64_t v_target_stride, const float* a_target_dev,
+                         int64_t target_env_stride, int64_t target_row_stride, const float* returns_dev,
+                         const float* nonterminals_dev, const float* support_dev, int32_t atoms, int32_t s_rows, int32_t batch,
+                         float gamma_n, float v_min, float v_max, float delta_z, float* m_dev, int64_t* a_star_dev, void* stream) {
+    if (!dueling_block_ok(v_online_dev, v_online_stride, a_online_dev, online_env_stride, online_row_stride, atoms, s_rows) ||
+        !dueling_block_ok(v_target_dev, v_target_stride, a_target_dev, target_env_stride, target_row_stride, atoms, s_rows) ||
+        !returns_dev || !nonterminals_dev || !support_dev || !m_dev || !a_star_dev || batch < 1 || !(v_max > v_min) ||
+        !(delta_z > 0))
+        return IRBPP_ERR_ARG;
+    size_t lds;
+    if (!dueling_lds((const void*)irbpp_dueling_target_kernel, atoms, s_rows, &lds)) return IRBPP_ERR_HIP;
+    hipLaunchKernelGGL(irbpp_dueling_target_kernel, dim3(batch), dim3(DUELING_THREADS), lds, (hipStream_t)stream, v_online_dev,
+                       (long long)v_online_stride, a_online_dev, (long long)online_env_stride, (long long)online_row_stride,
+                       v_target_dev, (long long)v_target_stride, a_target_dev, (long long)target_env_stride,
+                       (long long)target_row_stride, returns_dev, nonterminals_dev, support_dev, atoms, s_rows, gamma_n, v_min,
+                       v_max, delta_z, m_dev, a_star_dev);
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
 }
 

@@ -359,8 +359,8 @@ def masked_greedy_action(q: torch.Tensor, state: torch.Tensor, selected_action: 
 
 
 # Which form the two distributional-head wrappers below take on a HIP device when the caller does not say (use_hip=None).
-# The torch lines, until tools/c51_head_rates.py has shown on an MI355X that the kernels are not slower than them at 4096
-# environments ("The distributional head"): use_hip=True asks for the kernels.
+# The torch lines: tools/c51_head_rates.py on an MI355X found the act kernel faster than them at 4096 environments but slower
+# at 1024 ("The distributional head"; profiles/c51_head/): use_hip=True asks for the kernels.
 C51_HIP_DEFAULT = False
 
 
@@ -460,6 +460,117 @@ def c51_target(p_online: torch.Tensor, p_target: torch.Tensor, returns: torch.Te
                                             p_target.stride(1), _p(returns), _p(nonterminals), _p(support), atoms, S, B, float(gamma_n),
                                             float(v_min), float(v_max), float(delta_z), _p(m), _p(a_star), _stream(dev)),
                "irbpp_categorical_target")
+    return m, a_star
+
+
+# The same question for the two wrappers below, which start from the network's logits ("The dueling
+# head"): the kernels, since tools/dueling_head_rates.py measured them on an MI355X at 0.22 ms against 0.63 ms for the torch
+# lines (4096 envs) and 0.031 ms against 0.48 ms (a learn batch of 64), far outside the spread (profiles/dueling_head/).
+DUELING_HIP_DEFAULT = True
+
+
+def _dueling_lib(t: torch.Tensor, use_hip: Optional[bool]):
+    lib = _hip_lib(t.device)
+    if use_hip and lib is None:
+        raise RuntimeError("use_hip=True needs a HIP device")
+    return lib if (DUELING_HIP_DEFAULT if use_hip is None else use_hip) else None
+
+
+def _dueling_logits(v: torch.Tensor, a: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(v [N, atoms] or [N, 1, atoms], a [N, S, atoms]) -> v as [N, atoms]; shapes checked."""
+    if a.dim() != 3:
+        raise ValueError("a must be [N, S, atoms]")
+    N, _, atoms = a.shape
+    if v.dim() == 3 and v.shape[1] == 1:
+        v = v[:, 0]
+    if tuple(v.shape) != (N, atoms):
+        raise ValueError(f"v must be [{N}, {atoms}] (or [{N}, 1, {atoms}]) beside a {tuple(a.shape)}")
+    return v, a
+
+
+def _dueling_softmax(v: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
+    """model.py:395-400 (log=False) on v [N, atoms], a [N, S, atoms]."""
+    v = v.unsqueeze(1)
+    q = v + a - a.mean(1, keepdim=True)
+    return torch.softmax(q, dim=2)
+
+
+def _dueling_v(v: torch.Tensor) -> torch.Tensor:
+    v = v.to(torch.float32)
+    return v if v.stride(1) == 1 and v.stride(0) >= v.shape[1] else v.contiguous()
+
+
+def dueling_greedy_action(v: torch.Tensor, a: torch.Tensor, support: torch.Tensor, state: Optional[torch.Tensor] = None,
+                          selected_action: Optional[int] = None, q_out: Optional[torch.Tensor] = None,
+                          p_out: Optional[torch.Tensor] = None, *, use_hip: Optional[bool] = None) -> torch.Tensor:
+    """The end of DQNBPP.forward (model.py:395-400: ``v + a - a.mean(1)``, softmax over the atoms) and all of Agent.act after it
+    (agent.py:51-58), from the value logits ``v`` [N, atoms] (or [N, 1, atoms]) and the advantage logits ``a`` [N, S, atoms]
+    -> int64[N].  ``state`` / ``selected_action`` / ``q_out`` as in distributional_greedy_action; ``p_out`` (optional,
+    contiguous float32 [N, S, atoms]) receives the probabilities.  With ``use_hip=True`` (a HIP device; ``None`` takes
+    DUELING_HIP_DEFAULT) one kernel does all of it in a defined float32 arithmetic (irbpp_dueling_act: reproducible bit for
+    bit, the probabilities stay in LDS unless ``p_out`` is given); otherwise, and on the CPU, the reference's torch lines run."""
+    v, a = _dueling_logits(v, a)
+    N, S, atoms = a.shape
+    if selected_action is not None and int(selected_action) != S:
+        raise ValueError(f"selected_action {selected_action} != {S} candidate rows")
+    lib = _dueling_lib(a, use_hip)
+    if lib is None:
+        p = _dueling_softmax(v, a)
+        if p_out is not None:
+            p_out.copy_(p)
+        return distributional_greedy_action(p, support, state, selected_action, q_out, use_hip=False)
+    from . import _lib
+    v, a = _dueling_v(v), _c51_block(a)
+    support = support.to(device=a.device, dtype=torch.float32).contiguous()
+    obs_stride = 0
+    if state is not None:
+        state = state.to(torch.float32)
+        if state.stride(1) != 1:
+            state = state.contiguous()
+        obs_stride = state.stride(0)
+    q_stride = 0
+    if q_out is not None:
+        if q_out.dtype != torch.float32 or q_out.device != a.device or tuple(q_out.shape) != (N, S) or q_out.stride(1) != 1:
+            raise ValueError("q_out must be a float32 [N, S] tensor on a's device with contiguous rows")
+        q_stride = q_out.stride(0)
+    if p_out is not None and (p_out.dtype != torch.float32 or p_out.device != a.device or tuple(p_out.shape) != (N, S, atoms) or
+                              not p_out.is_contiguous()):
+        raise ValueError("p_out must be a contiguous float32 [N, S, atoms] tensor on a's device")
+    out = torch.empty((N,), dtype=torch.int64, device=a.device)
+    _lib.check(lib.irbpp_dueling_act(_p(v), v.stride(0), _p(a), a.stride(0), a.stride(1), _p(support), atoms, _p(state), obs_stride,
+                                     S, N, _p(out), _p(q_out), q_stride, _p(p_out), _stream(a.device)), "irbpp_dueling_act")
+    return out
+
+
+def dueling_c51_target(v_online: torch.Tensor, a_online: torch.Tensor, v_target: torch.Tensor, a_target: torch.Tensor,
+                       returns: torch.Tensor, nonterminals: torch.Tensor, support: torch.Tensor, gamma_n: float, v_min: float,
+                       v_max: float, *, use_hip: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Agent.learn's no_grad block (agent.py:90-115) from the logits of the online and the target network (each ``v``
+    [B, atoms] or [B, 1, atoms], ``a`` [B, S, atoms]) -> (m float32 [B, atoms], a_star int64 [B]); the other arguments as in
+    c51_target.  With ``use_hip=True`` (a HIP device; ``None`` takes DUELING_HIP_DEFAULT) one kernel does it
+    (irbpp_dueling_target: neither network's probabilities are written; of the target net's only row a_star is computed);
+    otherwise, and on the CPU, the reference's torch lines run."""
+    v_online, a_online = _dueling_logits(v_online, a_online)
+    v_target, a_target = _dueling_logits(v_target, a_target)
+    B, S, atoms = a_online.shape
+    if tuple(a_target.shape) != (B, S, atoms):
+        raise ValueError("a_online and a_target must have the same [B, S, atoms] shape")
+    lib = _dueling_lib(a_online, use_hip)
+    if lib is None:
+        return c51_target(_dueling_softmax(v_online, a_online), _dueling_softmax(v_target, a_target), returns, nonterminals,
+                          support, gamma_n, v_min, v_max, use_hip=False)
+    from . import _lib
+    dev = a_online.device
+    delta_z = (v_max - v_min) / (atoms - 1)
+    v_online, v_target, a_online, a_target = _dueling_v(v_online), _dueling_v(v_target), _c51_block(a_online), _c51_block(a_target)
+    f32 = lambda x: x.to(device=dev, dtype=torch.float32).contiguous()      # noqa: E731
+    returns, nonterminals, support = f32(returns.reshape(B)), f32(nonterminals.reshape(B)), f32(support)
+    m = torch.empty((B, atoms), dtype=torch.float32, device=dev)
+    a_star = torch.empty((B,), dtype=torch.int64, device=dev)
+    _lib.check(lib.irbpp_dueling_target(_p(v_online), v_online.stride(0), _p(a_online), a_online.stride(0), a_online.stride(1),
+                                        _p(v_target), v_target.stride(0), _p(a_target), a_target.stride(0), a_target.stride(1),
+                                        _p(returns), _p(nonterminals), _p(support), atoms, S, B, float(gamma_n), float(v_min),
+                                        float(v_max), float(delta_z), _p(m), _p(a_star), _stream(dev)), "irbpp_dueling_target")
     return m, a_star
 
 
