@@ -409,12 +409,21 @@ int irbpp_episode_metrics(const irbpp_episode_window* parts, int32_t n_parts, in
                           double* out_dev, void* stream);
 
 /* replaces: PackingGame.packed (binPhy.py:141,296), the per-episode placement record that
- * tools.test saves to trajs.npy (tools.py:339-340).  While set, every successful placement of
- * bin b, the i-th of its episode (i < capacity), stores meta_dev[b*capacity+i] =
- * item | rot<<16 | lx<<20 | ly<<24 (item ids must be < 65536) and z_dev[b*capacity+i] = its drop
- * height posZmap[rot,lx,ly].  A finished episode's entries stay readable until that bin's next
- * placement overwrites them, so read them right after the step that reported done.  NULL, NULL
- * switches the log off. */
+ * tools.test saves to trajs.npy (tools.py:339-340).  While set, every placement of bin b, the
+ * i-th of its episode (i < capacity), stores the word meta_dev[b*capacity+i] =
+ *   item (bits 0..15) | rot << 16 (bits 16..19) | lx << 20 (bits 20..24) | ly << 25 (bits 25..29)
+ * (bits 30..31 zero) and z_dev[b*capacity+i] = its drop height posZmap[rot,lx,ly].  Item ids must be
+ * < 65535; rot < 16 and lx, ly < 32 hold for every environment the library accepts (n_rot <= 8, action
+ * grids of at most 32 cells a side).
+ * The REFUSED placement that ends an episode is recorded too, as entry `counter` behind the episode's
+ * `counter` accepted ones (the reference appends to self.packed before it looks at `success`): its
+ * fields are masked to their widths, its item field is 0xFFFF when the trajectory was exhausted (no
+ * item to place), and its height is posZmap[rot,lx,ly] where the footprint lies inside the grid for
+ * that rotation and 1e3 where it does not.  An index i >= capacity is dropped, never wrapped: with
+ * capacity 0 nothing is written.  The index is the episode's own placement count, so a log attached
+ * in the middle of an episode continues at that episode's index.  A finished episode's entries stay
+ * readable until that bin's next placements overwrite them, so read them right after the step that
+ * reported done.  NULL, NULL switches the log off; one NULL pointer of the two is IRBPP_ERR_ARG. */
 int irbpp_set_placement_log(irbpp_env* env, uint32_t* meta_dev, double* z_dev, int32_t capacity);
 
 /* Caller side: the N per-env prioritised replay memories of main.py:61-63 as one tensor set.

@@ -107,7 +107,7 @@ struct State {
     uint32_t* cand;        // [N][S]
     BinState* bs;          // [N]
     double* totals;        // [N][4]: episodes, sum ratio, sum counter, sum reward
-    uint32_t* log_meta;    // optional [N][log_cap]: item | rot<<16 | lx<<20 | ly<<24 of the episode's placements
+    uint32_t* log_meta;    // optional [N][log_cap]: item (bits 0..15) | rot<<16 (4 bits) | lx<<20 (5 bits) | ly<<25 (5 bits) of the episode's placements
     double* log_z;         // optional [N][log_cap]: drop height of each placement
     int32_t log_cap;
     int32_t* order;        // [N] launch order of the bins (irbpp_item_order_kernel); identity until it has run

@@ -2992,8 +2992,11 @@ __device__ __forceinline__ void env_transition(const Params& P_run, const Tables
                 const int cursor = st_cursor;
                 const int slot = ps->item_idx;                       // self.packed.append(...) (binPhy.py:296)
                 if (ka->S.log_meta && slot < ka->S.log_cap) {
+                    // (a candidate row's cell lies on a grid of at most 32 x 32 cells: five bits each.  Said to the compiler so that it
+                    // packs the word from lx and ly as before, not from the key: otherwise the registers of the whole kernel move)
+                    __builtin_assume(lx < 32 && ly < 32);
                     ka->S.log_meta[(size_t)b * ka->S.log_cap + slot] = (uint32_t)item0 | ((uint32_t)rot << 16) |
-                                                                ((uint32_t)lx << 20) | ((uint32_t)ly << 24);
+                                                                ((uint32_t)lx << 20) | ((uint32_t)ly << 25);
                     ka->S.log_z[(size_t)b * ka->S.log_cap + slot] = z;
                 }
                 ps->ep_reward = epr;
@@ -3027,7 +3030,7 @@ __device__ __forceinline__ void env_transition(const Params& P_run, const Tables
                 if (ka->io.ep_len) ka->io.ep_len[b] = epl;
                 if (ka->S.log_meta && counter < ka->S.log_cap) {       // the refused placement is in self.packed too (binPhy.py:296)
                     ka->S.log_meta[(size_t)b * ka->S.log_cap + counter] = (uint32_t)(item0 & 0xFFFF) | ((uint32_t)(rot & 15) << 16) |
-                                                                   ((uint32_t)(lx & 15) << 20) | ((uint32_t)(ly & 15) << 24);
+                                                                   ((uint32_t)(lx & 31) << 20) | ((uint32_t)(ly & 31) << 25);
                     ka->S.log_z[(size_t)b * ka->S.log_cap + counter] = z;
                 }
                 double* tot = ka->S.totals + (size_t)b * 4;
@@ -3290,8 +3293,12 @@ __device__ __forceinline__ void apply_body(const Params& P, const Tables& T, con
             const int epl = ps->ep_len + 1;
             const int slot_i = ps->item_idx;                         // self.packed.append(...) (binPhy.py:296)
             if (ka->S.log_meta && slot_i < ka->S.log_cap) {
+                // (the cell -- a candidate row's, the caller's clamped one, the heuristic's -- lies on a grid of at most 32 x 32 cells:
+                // five bits each.  Said to the compiler so that it packs the word from lx and ly as before, not from the key:
+                // otherwise the registers of the whole kernel move)
+                __builtin_assume(lx < 32 && ly < 32);
                 ka->S.log_meta[(size_t)b * ka->S.log_cap + slot_i] = (uint32_t)item0 | ((uint32_t)rot << 16) |
-                                                              ((uint32_t)lx << 20) | ((uint32_t)ly << 24);
+                                                              ((uint32_t)lx << 20) | ((uint32_t)ly << 25);
                 ka->S.log_z[(size_t)b * ka->S.log_cap + slot_i] = z;
             }
             ps->ep_reward = epr;
@@ -3324,7 +3331,7 @@ __device__ __forceinline__ void apply_body(const Params& P, const Tables& T, con
             if (ka->io.ep_len) ka->io.ep_len[b] = epl;
             if (ka->S.log_meta && counter < ka->S.log_cap) {           // the refused placement is in self.packed too (binPhy.py:296)
                 ka->S.log_meta[(size_t)b * ka->S.log_cap + counter] = (uint32_t)(item0 & 0xFFFF) | ((uint32_t)(rot & 15) << 16) |
-                                                               ((uint32_t)(lx & 15) << 20) | ((uint32_t)(ly & 15) << 24);
+                                                               ((uint32_t)(lx & 31) << 20) | ((uint32_t)(ly & 31) << 25);
                 ka->S.log_z[(size_t)b * ka->S.log_cap + counter] = z;
             }
             double* tot = ka->S.totals + (size_t)b * 4;

@@ -14,6 +14,9 @@
 //   trace_border_wide, approx_and_convex_t<uint16_t, 5>: host-tested against the oracle), candidate rows in np.unique order,
 //   the > S selection / the no-candidate fallback by a radix select over keys in LDS, rows, candidate keys, fused MINZ policy.
 //
+// Nothing in this file writes the placement log: a wide step's placement -- and its log entry, lx and ly up to 31 in five bits each --
+// is irbpp_apply_kernel's (launch_apply in irbpp_capi.hip; apply_body in irbpp_kernels.hip), pinned in tests/test_gpu_placement_log.py.
+//
 // Same arithmetic, same order of operations as the 16 x 16 pipeline; parity against both oracles in tests/test_gpu_wide.py.
 #pragma once
 

@@ -30,6 +30,16 @@ def rotation_quaternion_xyzw(rot_idx: int) -> np.ndarray:
     return np.array([0.0, 0.0, z, w])
 
 
+def decode_placement_words(words):
+    """(item, rot, lx, ly) of placement-log words (include/irbpp.h, irbpp_set_placement_log): item in bits 0..15
+    (0xFFFF: the trajectory was exhausted, nothing to place), rot in 16..19, lx in 20..24, ly in 25..29.  ``words``: a torch
+    tensor (any device; the int32 tensor ``enable_placement_log`` hands out) or an array; four int64 numpy arrays of its shape."""
+    if isinstance(words, torch.Tensor):
+        words = words.cpu().numpy()
+    w = np.asarray(words).astype(np.int64) & 0xFFFFFFFF
+    return w & 0xFFFF, (w >> 16) & 15, (w >> 20) & 31, (w >> 25) & 31
+
+
 def evaluate(shapes, sequences, n_episodes: int, *, policy: Optional[Callable] = None,
              order_policy: Optional[Callable] = None, device="cuda:0",
              names: Optional[Dict[int, str]] = None, traj_start: int = 1, max_steps: int = 4096,
@@ -82,15 +92,14 @@ def evaluate(shapes, sequences, n_episodes: int, *, policy: Optional[Callable] =
         newly = h["done"] & ~finished
         if newly.any():
             idx = np.nonzero(newly)[0]
-            m = meta[idx].cpu().numpy().astype(np.uint32)
+            m_item, m_rot, m_lx, m_ly = decode_placement_words(meta[idx])
             z = logz[idx].cpu().numpy()
             for row, b in enumerate(idx):
                 k = int(h["counter"][b])
                 ratio[b], reward_sum[b], length[b] = h["ratio"][b], h["ep_reward"][b], h["ep_len"][b]
                 ep = []
                 for i in range(min(k + 1, log_capacity)):        # k accepted placements + the refused one
-                    w = int(m[row, i])
-                    item, rot, lx, ly = w & 0xFFFF, (w >> 16) & 15, (w >> 20) & 15, (w >> 24) & 15
+                    item, rot, lx, ly = int(m_item[row, i]), int(m_rot[row, i]), int(m_lx[row, i]), int(m_ly[row, i])
                     if item == 0xFFFF:                            # trajectory exhausted: no item to place (None)
                         break
                     flb = np.round((lx * res_a, ly * res_a, bin_z), decimals=6) * scale     # addObject (Interface.py:201)

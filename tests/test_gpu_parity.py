@@ -589,6 +589,9 @@ def test_batched_evaluation_matches_sequential_reference_protocol():
         assert len(out["trajs"][ep]) == len(placed) == info["counter"] + 1
         for got, (item, rot, lx, ly, height) in zip(out["trajs"][ep], placed):
             assert got[0] == item and got[1] == "%d.obj" % item
+            flb = np.round((lx * 0.02, ly * 0.02, 0.30), decimals=6) * 100.0        # addObject (Interface.py:201), x scale
+            flb[2] = height * 100.0                                                  # adjustHeight (Interface.py:185-187)
+            np.testing.assert_array_equal(got[2], flb / 100.0)                       # (the log's height is the oracle's, bit for bit)
             np.testing.assert_allclose(got[2], [lx * 0.02, ly * 0.02, height], rtol=0, atol=1e-12)
             np.testing.assert_array_equal(got[3], rotation_quaternion_xyzw(rot))
     assert abs(out["mean_ratio"] - np.mean(out["ratio"])) < 1e-15

@@ -6,7 +6,9 @@ out) are identical -- the check a change that must leave existing kernels alone 
     python tools/kernel_instruction_diff.py BEFORE.so AFTER.so [substring ...]
 
 Kernels present in one library only are listed as such; with substrings only the kernels whose name contains one of
-them are listed.  Exit code 1 if a kernel present in both differs.
+them are listed.  A kernel whose two streams have the same mnemonics and the same registers, instruction for instruction,
+and differ in literal operands alone is reported as "immediates only", followed by the instructions concerned.
+Exit code 1 if a kernel present in both differs.
 """
 import os
 import re
@@ -23,6 +25,14 @@ def streams(path):
     return out
 
 
+LITERAL_RE = re.compile(r"(?<![\w\[:])(0x[0-9a-fA-F]+|\d+)(?![\w\]:])")
+
+
+def masked(stream):
+    """The stream with every literal operand (not a register number or range) blanked."""
+    return [(m, LITERAL_RE.sub("#", ops)) for m, ops in stream]
+
+
 def main(argv):
     before, after, want = streams(argv[1]), streams(argv[2]), argv[3:]
     differ = 0
@@ -35,6 +45,12 @@ def main(argv):
             continue
         same = a == b
         differ += not same
+        if not same and len(a) == len(b) and masked(a) == masked(b):
+            pairs = [(x, y) for x, y in zip(a, b) if x != y]
+            print(f"{name}: {len(a)} -> {len(b)} instructions, immediates only ({len(pairs)} instructions)")
+            for (m, x), (_, y) in pairs:
+                print(f"    {m} {x}  ->  {y}")
+            continue
         print(f"{name}: {len(a)} -> {len(b)} instructions, {'identical' if same else 'DIFFERENT'}")
     return 1 if differ else 0
 
