@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include <new>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -25,6 +26,7 @@
 #include "irbpp_dueling.hip"        // the same from the network's logits: dueling combine + softmax fused in (irbpp_dueling_act, irbpp_dueling_target)
 #include "irbpp_metrics.hip"        // the trainer's episode metrics (irbpp_set_episode_window)
 #include "irbpp_itemgen.h"
+#include "irbpp_plan.h"             // which kernels a transition launches: the registry of kernels and plan_transition
 
 using namespace irbpp;
 
@@ -65,6 +67,19 @@ struct irbpp_env {
 
 namespace {
 
+static_assert(PLAN_KEY_CAND == KEY_CAND && PLAN_KEY_CELLS == KEY_CELLS && PLAN_KEY_HEUR == KEY_HEUR &&
+              PLAN_TRACE_REFILL_BATCH == TRACE_REFILL_BATCH, "irbpp_plan.h restates these constants of irbpp_kernels.hip");
+// the function behind every KernelId of irbpp_plan.h's list (nullptr: a specialised build this library was compiled without)
+#define IRBPP_X(id, scope, name, threads, lds) (const void*)scope name,
+#ifdef IRBPP_NO_SPEC
+#define IRBPP_XS(id, scope, name, threads, lds) nullptr,
+#else
+#define IRBPP_XS IRBPP_X
+#endif
+const void* const kernel_registry[N_KERNELS] = {IRBPP_KERNEL_LIST(IRBPP_X, IRBPP_XS)};
+#undef IRBPP_X
+#undef IRBPP_XS
+
 template <typename T>
 int dev_alloc(irbpp_env* env, T** out, size_t count) {
     void* p = nullptr;
@@ -86,9 +101,6 @@ int dev_upload(irbpp_env* env, const T** out, const T* host, size_t count) {
 }
 
 inline double round6_host(double x) { return nearbyint(x * 1e6) / 1e6; }   // np.round(x, 6)
-constexpr int TRACE_SMALL_GRID = 8192;      // waves of a trace launch over few bins (16 or 32 candidates per wave)
-constexpr int TRACE_CPW16_BINS = 0;         // launches over at most this many bins trace 16 candidates per wave ...
-constexpr int TRACE_CPW32_BINS = 1024;      // ... 32 per wave (profiles/r04 session 41: +1.5 ... 1.9 % at 512 / 1024 bins, -0.3 % at 2048; 16 per wave loses everywhere)
 // dynamic-LDS carve-up of the transition kernel: irbpp::layout_lds (irbpp_device.h, shared with the specialised builds)
 void layout_lds_host(Params& P) {
     int pad = 0;
@@ -101,51 +113,14 @@ void layout_lds_host(Params& P) {
 // The dynamic-LDS limit is an attribute of the kernel on the device, not of an environment: always raise it to the
 // CU's 160 KiB, so that a later, smaller environment cannot lower it under one that is still alive.
 int raise_lds_limits() {
-    const void* kernels[] = {(const void*)irbpp_env_kernel_wide, (const void*)irbpp_env_kernel, (const void*)irbpp_env_kernel_box,
-                             (const void*)irbpp_env_kernel_box8, (const void*)irbpp_env_kernel_generic,
-                             (const void*)irbpp_env_kernel_generic8, (const void*)irbpp_env_kernel_mixed8, (const void*)irbpp_hull_kernel,
-                             (const void*)irbpp_env_kernel_chain, (const void*)irbpp_wide_kernel,
-#if !defined(IRBPP_NO_SPEC)
-                             (const void*)irbpp_env_kernel_s1, (const void*)irbpp_env_kernel_s2, (const void*)irbpp_env_kernel_s3,
-                             (const void*)irbpp_env_kernel_s4, (const void*)irbpp_env_kernel_s5, (const void*)irbpp_emit_kernel_s5,
-                             (const void*)irbpp_env_kernel_chain_s1, (const void*)wg128::irbpp_env_kernel_s1_w128,
-                             (const void*)irbpp_emit_kernel_s1, (const void*)irbpp_emit_kernel_s2,
-                             (const void*)irbpp_emit_kernel_s3, (const void*)irbpp_emit_kernel_s4,
-                             (const void*)irbpp_emit_wave_kernel_s1, (const void*)irbpp_emit_wave_kernel_s2, (const void*)irbpp_emit_wave_kernel_s5,
-                             (const void*)wg512::irbpp_env_kernel_s4_w512, (const void*)wg512::irbpp_env_kernel_s4_w512c,
-#endif
-                             (const void*)wg512::irbpp_env_kernel_generic_w512,
-                             (const void*)irbpp_emit_wave_kernel,
-                             (const void*)irbpp_emit_kernel, (const void*)irbpp_heuristic_kernel};
-    for (const void* k : kernels)
-        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return IRBPP_ERR_HIP;
+    for (int id = 0; id < N_KERNELS; ++id)
+        if (kernel_info(id).raise_lds && kernel_registry[id] != nullptr &&
+            hipFuncSetAttribute(kernel_registry[id], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+            return IRBPP_ERR_HIP;
     return IRBPP_OK;
 }
 
 }  // namespace
-
-// lattice data through and through (every rotation on the block path) or box data: what the wave-per-bin emit kernel and the
-// early split of the apply phase are for; a data set with list rotations (PATH_MIXED) is treated like free-form data there
-// radix counters / sort keys of the emit routine's > S selection, behind the transition kernel's carve-up (CHAIN builds): the
-// emit kernel's own e_hist region (irbpp_device.h: layout_lds)
-static int chain_extra_lds(const Params& P) {
-    int npad = 64;
-    while (npad < P.S) npad <<= 1;
-    return align16(10 * npad > 1024 ? 10 * npad : 1024);
-}
-static bool all_block(const Params& P) { return P.block_b > 0 && P.block_rots == (1 << P.R) - 1; }
-static bool lattice_or_box(const Params& P) { return all_block(P) || P.box != 0; }
-// ... except in what its level images look like: unions of rectangles with a few dozen candidates per bin, practically never more
-// than S of them -- the wave-per-bin emit kernel's case, not the speckled free-form images the heavy-first list is for
-static bool lattice_images(const Params& P) { return P.block_b > 0 || P.box != 0; }
-
-// waves of the largest trace grid a launch over this environment's bins can ask for (16 candidates per wave: four waves per
-// bin), at most TRACE_SMALL_GRID of them beyond one per bin: State::w_big holds one scratch per wave of the grid (9 KB each:
-// a 1-bin probe environment allocates 37 KB, not 76 MB)
-static int trace_grid_cap(int N) {
-    const int small = 4 * N < TRACE_SMALL_GRID ? 4 * N : TRACE_SMALL_GRID;
-    return N > small ? N : small;
-}
 
 extern "C" {
 
@@ -552,258 +527,53 @@ int irbpp_obs_len(const irbpp_env* env, int32_t which) {
     return which == 0 ? env->P.obs_len0 : env->P.obs_len1;
 }
 
-// The transition kernel is compiled once per overlap path (lattice blocks, solid boxes, generic cell lists), with and
-// without the 64-VGPR cap that makes eight workgroups per CU resident, plus one build that decides at run time.
 typedef void (*env_kernel_fn)(const Params, const Tables, const State, const StepIO, const int);
-struct EnvKernel { env_kernel_fn fn; const char* name; int threads = 256; };
-// Specialised builds (irbpp_device.h): SPEC index whose compile-time constants equal this environment's Params, or 0.
-static int pick_spec(const irbpp_env* env) {
-#if defined(IRBPP_NO_SPEC) || defined(IRBPP_ABLATE)
-    return 0;
-#else
-    if (env->cfg.tuning & (IRBPP_TUNE_NO_SPECIALISED | IRBPP_TUNE_WIDE_KERNEL | IRBPP_TUNE_NARROW_KERNEL)) return 0;
-    static const Params spec[N_SPECS] = {Params{}, spec_params(SPEC_KEYS[1]), spec_params(SPEC_KEYS[2]), spec_params(SPEC_KEYS[3]),
-                                         spec_params(SPEC_KEYS[4]), spec_params(SPEC_KEYS[5])};
-    static_assert(N_SPECS == 6, "one table entry and one kernel per SPEC_KEYS row");
-    for (int i = 1; i < N_SPECS; ++i)
-        if (spec_matches(env->P, spec[i])) return i;
-    return 0;
-#endif
-}
+typedef void (*trace_kernel_fn)(const Params, const State, long long*);
 
-// step(): the actions are applied by irbpp_apply_kernel (a wave per bin) and the transition kernel only observes
-// (MODE_OBSERVE), unless the stability proxy is on (it rates the placement on the LDS tile) or the caller asks for the fused form
-// -- from the launch size on at which that pays.  The apply kernel costs a launch and one pass of its dependent reads
-// (~9 us at any size, 15 us with free-form footprints); inside the transition kernel the same chain is paid once per ROUND
-// of workgroups (eight per CU), hidden in part behind the other workgroups' arithmetic.  Measured on the specialised builds
-// (profiles/r05/s6, placement-steps/s split vs fused): BlockOut 2048 / 4096 / 6144 / 8192 / 16384 bins -4 % / 0 / +1.7 /
-// +3.0 / +6.1 %; cube 4096 / 8192: 0 / +2.7 %; free-form solids at R = 8: 4096 -1.1 %, 8192 +0.3 % (BlockOut at R = 8: 0 /
-// +1.6 %); the 64 x 64 heightmap (four workgroups per CU, footprints of up to 1600 cells): -2 % at two and at four rounds;
-// a buffered step (K > 1: the apply phase and a float32 copy of the tile) with a WAVE per bin: -22 % / -52 % (one wave takes
-// 16 dependent round trips to copy the tile) -- with a WORKGROUP per bin (irbpp_apply_wg_kernel: wave 0 applies, all four
-// waves copy; no LDS tile, no overlap-test code in the kernel) it wins at every size, see profiles/r05/s25.  With a second
-// group of bins on another stream the split pays a round earlier (BlockOut as two groups of 4096: 59.1 -> 60.5 M,
-// profiles/r05/s10).  Hence, for online steps: lattice and box data from two rounds of workgroups on, cell lists from four
-// rounds on where eight workgroups share a CU.
-static bool split_apply(const irbpp_env* env, int n) {
-    if (env->P.stability != 0 || (env->cfg.tuning & IRBPP_TUNE_FUSED_APPLY)) return false;
-    if (env->cfg.tuning & IRBPP_TUNE_SPLIT_APPLY) return true;
-    if (env->P.K > 1) return true;                 // buffered: the workgroup-per-bin form (apply + order observation), at every size
-    const int per_cu = (160 * 1024) / (env->P.lds_bytes > 0 ? env->P.lds_bytes : 1);
-    if (per_cu < 8) return false;
-    const bool lists = !lattice_or_box(env->P);
-    return n >= (lists ? 4 : 2) * 256 * 8;
-}
-
-static EnvKernel pick_env_kernel(const irbpp_env* env) {
-    const Params& P = env->P;
-    const int t = env->cfg.tuning;
-    const bool lds_allows_8 = 8 * P.lds_bytes <= 160 * 1024;
-    // Generic path where the tile is so large that at most four 256-thread workgroups fit a CU's LDS (the 64 x 64 heightmap:
-    // 40 KB per bin): 512-thread workgroups, eight waves on one tile (irbpp::wg512, the second pass of irbpp_kernels.hip)
-    const bool generic = P.block_b == 0 && !P.box;
-    const bool mixed = P.block_b > 0 && !all_block(P);
-#if !defined(IRBPP_NO_SPEC) && !defined(IRBPP_ABLATE)
-    if (generic && (t & IRBPP_TUNE_NARROW_KERNEL) && (t & IRBPP_TUNE_WG512) && spec_matches(P, spec_params(SPEC_KEYS[4])))
-        return {wg512::irbpp_env_kernel_s4_w512c, "irbpp_env_kernel_s4_w512c", 512};      // (A/B: under the 64-VGPR cap)
-#endif
-    const bool wg512 = generic && !(t & (IRBPP_TUNE_NO_WG512 | IRBPP_TUNE_WIDE_KERNEL | IRBPP_TUNE_NARROW_KERNEL)) &&
-                       ((t & IRBPP_TUNE_WG512) || 5 * P.lds_bytes > 160 * 1024);
-#if !defined(IRBPP_NO_SPEC) && !defined(IRBPP_ABLATE)
-    // (under the 64-VGPR cap four such workgroups share a CU instead of three: level at 2048 bins, +10 % at 8192, profiles/r05/s30)
-    if (wg512 && pick_spec(env) == 4)
-        return P.N >= 4096 ? EnvKernel{wg512::irbpp_env_kernel_s4_w512c, "irbpp_env_kernel_s4_w512c", 512}
-                           : EnvKernel{wg512::irbpp_env_kernel_s4_w512, "irbpp_env_kernel_s4_w512", 512};
-#endif
-    if (wg512 && (pick_spec(env) == 0 || (t & IRBPP_TUNE_WG512)))
-        return {wg512::irbpp_env_kernel_generic_w512, "irbpp_env_kernel_generic_w512", 512};
-#if !defined(IRBPP_NO_SPEC) && !defined(IRBPP_ABLATE)
-    if ((t & IRBPP_TUNE_WG128) && pick_spec(env) == 1)
-        return {wg128::irbpp_env_kernel_s1_w128, "irbpp_env_kernel_s1_w128", 128};        // (A/B: two waves per bin)
-    switch (pick_spec(env)) {            // (a key fixes the overlap path: block_b and box are pinned fields)
-        case 1: return {irbpp_env_kernel_s1, "irbpp_env_kernel_s1"};
-        case 2: return {irbpp_env_kernel_s2, "irbpp_env_kernel_s2"};
-        case 3: return {irbpp_env_kernel_s3, "irbpp_env_kernel_s3"};
-        case 4: return {irbpp_env_kernel_s4, "irbpp_env_kernel_s4"};
-        case 5: return {irbpp_env_kernel_s5, "irbpp_env_kernel_s5"};
-        default: break;
-    }
-#endif
-    if (mixed) return (t & IRBPP_TUNE_WIDE_KERNEL) ? EnvKernel{irbpp_env_kernel_wide, "irbpp_env_kernel_wide"} : EnvKernel{irbpp_env_kernel_mixed8, "irbpp_env_kernel_mixed8"};
-    if (P.block_b > 0) {
-        if ((t & IRBPP_TUNE_WIDE_KERNEL) || 6 * P.lds_bytes > 150 * 1024) return {irbpp_env_kernel_wide, "irbpp_env_kernel_wide"};
-        return {irbpp_env_kernel, "irbpp_env_kernel"};
-    }
-    if (P.box) {
-        if (t & IRBPP_TUNE_WIDE_KERNEL) return {irbpp_env_kernel_box, "irbpp_env_kernel_box"};
-        if ((t & IRBPP_TUNE_NARROW_KERNEL) || lds_allows_8) return {irbpp_env_kernel_box8, "irbpp_env_kernel_box8"};
-        return {irbpp_env_kernel_box, "irbpp_env_kernel_box"};
-    }
-    // generic path: the build under the 64-VGPR cap where the LDS lets an eighth workgroup onto the CU (general 15.1 vs
-    // 14.9 M steps/s, blockout at R = 8 20.4 vs 20.1 M with the blocked and pipelined loop; before it the seven-wave
-    // build was ahead, 12.9 vs 12.2 M); a 64 x 64 heightmap (40 KB, four workgroups) gains nothing from the cap
-    if (t & IRBPP_TUNE_WIDE_KERNEL) return {irbpp_env_kernel_generic, "irbpp_env_kernel_generic"};
-    if ((t & IRBPP_TUNE_NARROW_KERNEL) || lds_allows_8) return {irbpp_env_kernel_generic8, "irbpp_env_kernel_generic8"};
-    return {irbpp_env_kernel_generic, "irbpp_env_kernel_generic"};
-}
-
-// Border following: candidates per wave and grid of a launch over n bins.  A bin averages a few dozen candidate starts; at
-// full width (thousands of bins) 64 per wave fill every SIMD and fewer, shorter-lived waves only add scheduling overhead
-// (measured at 4096 bins: 28.3 / 26.8 / 24.3 M steps/s for 64 / 32 / 16); a launch over few bins leaves SIMDs idle, and a
-// wave lasts as long as the longest of its borders, so there the candidates are spread over more waves.
-static int pick_trace_cpw(const irbpp_env* env, int n) {
-    const int t = env->cfg.tuning;
-    if (t & IRBPP_TUNE_TRACE_CPW64) return 64;
-    if (t & IRBPP_TUNE_TRACE_CPW32) return 32;
-    if (t & IRBPP_TUNE_TRACE_CPW16) return 16;
-    if (t & IRBPP_TUNE_TRACE_REFILL) return TRACE_REFILL_BATCH;
-    // (lane refill -- a wave owns a batch of 128 candidates and hands a lane the next one as borders close, trace_refill_body --
-    // is OPT-IN: measured slower at every size, profiles/r06/LOG.md session 2: 8192 BlockOut bins 54.9 -> 51.4 M as one group,
-    // 63.8 -> 59.0 M as two, the kernel 36.2 -> 46.0 us.  The chip has as many lane slots as a launch has candidates, so a
-    // refilled lane's work is taken from another wave, not from idleness, and one wave then pays every refill's latencies in turn)
-    return n <= TRACE_CPW16_BINS ? 16 : (n <= TRACE_CPW32_BINS ? 32 : 64);
-}
-
-// One kernel per observation (OPT-IN, IRBPP_TUNE_CHAIN): the bin's own workgroup finishes its observation (CHAIN builds of the
-// transition kernel: contour stage and candidate rows in LDS, no trace / polygon / emit launches).  Built for launches of up to
-// ~2048 bins, where a step is a chain of launch and drain latencies whatever the number of bins, and measured SLOWER there
-// (profiles/r06/LOG.md session 6, placement-steps/s one kernel vs four): a buffered placement at 512 / 1024 / 2048 bins 8.1 vs
-// 9.0 / 12.8 vs 16.3 / 16.5 vs 25.9 M, BlockOut online at 1024 / 2048 bins 14.4 vs 18.7 / 18.0 vs 29.7 M, free-form solids at
-// 1024 bins 3.2 vs 8.7 M; only the Cube set gains (26.7 vs 24.4 M at 1024 bins).  A bin's observation is ~25 borders to follow
-// and approximate: inside its own workgroup that is one serial latency chain per bin on a CU with nobody else to issue,
-// while the split kernels spread the borders of ALL bins over every SIMD of the chip; the launch boundaries they pay
-// (~3 us each) are the smaller price.
-static bool chain_launch(const irbpp_env* env, int n) {
-    const int t = env->cfg.tuning;
-    (void)n;
-    if (!(t & IRBPP_TUNE_CHAIN) || env->P.stability != 0) return false;
-    if (t & (IRBPP_TUNE_TRACE_CPW64 | IRBPP_TUNE_TRACE_CPW32 | IRBPP_TUNE_TRACE_CPW16 | IRBPP_TUNE_TRACE_REFILL | IRBPP_TUNE_INLINE_POLYGON |
-             IRBPP_TUNE_BLOCK_EMIT | IRBPP_TUNE_WAVE_EMIT | IRBPP_TUNE_SPLIT_APPLY | IRBPP_TUNE_GRAPH | IRBPP_TUNE_WG512 | IRBPP_TUNE_NARROW_KERNEL))
-        return false;                                          // (a caller that forces a shape of the split pipeline gets the split pipeline)
-    if (env->P.lds_bytes > 32 * 1024) return false;            // (the 64 x 64 heightmap: 512-thread workgroups on a 40 KB tile, not this)
-    return true;
-}
-
-// The apply phase of a split step over n launch slots: a wave per bin, or (buffered environments below 2048 bins) a workgroup per
-// bin; `key` says where the placements' cells come from (ApplyKey: candidate rows, the caller's cells, the heuristic's choice).
-// irbpp_heuristic_step's selection is fused into the placing wave (irbpp_apply_heur_kernel) for MINZ / DBLF / FIRSTFIT (as a kernel
-// of its own in front of the cell apply it measured slower at every size, DESIGN.md "Placing at grid cells"); HM keeps the
-// recomputing scorer (it needs the heightmap window sums): it writes the triples to env->heur_cells, which
-// irbpp_apply_cells_kernel reads behind it on the same stream.  The scorer indexes bins by workgroup, without block_off: a
-// heuristic step always covers the whole environment (launch_env refuses any other grid for KEY_HEUR).
-static void launch_apply(irbpp_env* env, StepIO io, int mode, hipStream_t st, int n, int key) {
-    if (key == KEY_HEUR && io.heur_method == 4) {
-        StepIO sel = io;
-        sel.heur_out = env->heur_cells;
-        hipLaunchKernelGGL(irbpp_heuristic_kernel, dim3(env->P.N), dim3(256), env->P.lds_bytes_full, st, env->P, env->T, env->S, sel);
-        io.actions = env->heur_cells;
-        key = KEY_CELLS;
-    }
-    const bool wg = env->P.K > 1 && n < 2048;
-    env_kernel_fn fn = wg ? irbpp_apply_wg_kernel : irbpp_apply_kernel;
-    if (key == KEY_CELLS) fn = wg ? irbpp_apply_cells_wg_kernel : irbpp_apply_cells_kernel;
-    if (key == KEY_HEUR) fn = wg ? irbpp_apply_heur_wg_kernel : irbpp_apply_heur_kernel;
-    hipLaunchKernelGGL(fn, wg ? dim3(n) : dim3((n + 3) / 4), dim3(256), 0, st, env->P, env->T, env->S, io, mode);
-}
-
-// One launch group: the launch slots [first, first + n) of a transition -- order (for step / candidates), the
-// transition kernel and, in the split pipeline, trace and emit -- on one stream.
-// key != KEY_CAND (irbpp_step_cells / irbpp_heuristic_step): always the apply kernel followed by MODE_OBSERVE, whatever the size.
-static void launch_group(irbpp_env* env, StepIO io, int mode, hipStream_t st, int first, int n, int key = KEY_CAND) {
-    io.block_off = first;
+// One launch group: the launches of a transition's plan (irbpp_plan.h: plan_transition) over n launch slots, on one stream;
+// `rows`: the per-bin row counts of io.obs where that is a registered observation buffer, else null.
+// Most kernels take (Params, Tables, State, StepIO, mode); the few that do not have their own case.
+static void launch_group(irbpp_env* env, StepIO io, const Plan& plan, int32_t* rows, hipStream_t st, int n) {
+    io.block_off = 0;
     io.n_slots = n;
     io.auto_action = env->auto_actions;
-    io.use_order = 0;
-    if (mode == MODE_STEP && env->item_order && first == 0 && n == env->P.N) {
-        hipLaunchKernelGGL(irbpp_item_order_kernel, dim3(1), dim3(1024), 0, st, env->T, env->S, n);
-        io.use_order = 1;
-    }
-    io.obs_rows = nullptr;
-    const bool observes = mode == MODE_CANDS || ((mode == MODE_RESET || mode == MODE_STEP) && env->P.K == 1);
-    for (auto& rb : env->obs_buffers)
-        if (rb.first == io.obs) {
-            // reset_specific writes a row per LISTED bin and a buffered environment's step / reset write the order
-            // observation: through a registered pointer either leaves the per-bin row counts meaningless
-            if (observes && !(mode == MODE_RESET && io.bin_list != nullptr)) io.obs_rows = rb.second;
-            else hipMemsetAsync(rb.second, 0xFF, (size_t)env->P.N * sizeof(int32_t), st);
-        }
-    // split pipeline: a location observation is finished by the trace kernel (one wave per 64 candidate starts of
-    // the launch's flat list) and the emit kernel (one workgroup per bin), on the same stream
-    if (env->P.wide) {                     // irbpp_wide.hip: [the geometry-free apply kernel,] then ONE kernel per observation
-        int wmode = mode;
-        if (mode == MODE_STEP) {
-            launch_apply(env, io, mode, st, n, key);
-            if (env->P.K > 1) return;
-            wmode = MODE_OBSERVE;
-        }
-        hipLaunchKernelGGL(irbpp_wide_kernel, dim3(n), dim3(256), wide_layout(env->P).bytes, st, env->P, env->T, env->S, io, wmode);
-        return;
-    }
-    const bool chain = observes && mode != MODE_POSSIBLE && chain_launch(env, n);
-    const bool split = env->P.split && observes && !chain;
-    // expensive bins first in the emit kernel: free-form level images only (lattice and box data never get there), not for a
-    // listed reset (its observation rows go by list position)
-    const bool heavy_first = split && env->P.heavy_cap > 0 && !lattice_images(env->P) && io.bin_list == nullptr &&
-                             !(env->cfg.tuning & IRBPP_TUNE_NO_HEAVY_FIRST);
-    io.heavy_turn = heavy_first ? env->heavy_turn : -1;
-    if (heavy_first) env->heavy_turn ^= 1;
-    int env_mode = mode;
-    if (chain && !(mode == MODE_STEP && env->P.K > 1)) {
-        // (a buffered step is the apply kernel below: it observes nothing)
-        const bool s1 = pick_spec(env) == 1;
-        hipLaunchKernelGGL(s1 ? irbpp_env_kernel_chain_s1 : irbpp_env_kernel_chain, dim3(n), dim3(256), env->P.lds_bytes + chain_extra_lds(env->P), st,
-                           env->P, env->T, env->S, io, mode);
-        return;
-    }
-    if (mode == MODE_STEP && (key != KEY_CAND || split_apply(env, n))) {
-        // a buffered step: a workgroup per bin at launches of fewer than 2048 bins (a wave per bin leaves most of the chip
-        // to one dependent chain per CU there: 15.7 vs 15.3 M at 1024 bins), a wave per bin from there on (every bin resident
-        // at once: 8192 bins as two groups 50.6 -> 55.2 M, 4096 bins 40.0 -> 41.6 M; profiles/r05/s27)
-        launch_apply(env, io, mode, st, n, key);
-        env_mode = MODE_OBSERVE;         // (a buffered step ends with the apply kernel: it wrote the order observation)
-    }
-    if (!(env_mode == MODE_OBSERVE && env->P.K > 1)) {
-        const EnvKernel ek = pick_env_kernel(env);
-        hipLaunchKernelGGL(ek.fn, dim3(n), dim3(ek.threads), env->P.lds_bytes, st, env->P, env->T, env->S, io, env_mode);
-    }
-    if (split) {
-        // the grid covers an average of up to 64 candidates per bin and strides over the chunks beyond that
-        // one trace wave per 64 candidates a bin may average, two polygon waves per bin; the kernels stride over anything
-        // beyond (half / a third of either grid with striding measured -4 ... -9 %)
-        const int cpw = pick_trace_cpw(env, n), pgrid = 2 * n;
-        // (IRBPP_TUNE_INLINE_POLYGON: every trace wave runs approxPolyDP on the borders it followed itself -- the path a full
-        // record list takes -- and no polygon kernel is launched.  Measured at 1024 / 2048 / 4096 bins: 11.8 / 20.2 / 28.8 M
-        // steps/s against 13.9 / - / 31.1 M: the approximation stretches the slowest trace waves.  For the parity tests.)
-        const int tune = env->cfg.tuning;
-        const bool inline_polygon = (tune & IRBPP_TUNE_INLINE_POLYGON) != 0;
-        Params Pt = env->P;
-        if (inline_polygon) Pt.round_cap = 0;
-        int tgrid = cpw > 64 ? (n * 64 + cpw - 1) / cpw : n * (64 / cpw);
-        if (tgrid > trace_grid_cap(env->P.N)) tgrid = trace_grid_cap(env->P.N);      // (w_big holds one scratch per wave of the grid)
-        auto trace_fn = cpw > 64 ? irbpp_trace_kernel_refill : cpw == 64 ? irbpp_trace_kernel : (cpw == 32 ? irbpp_trace_kernel_c32 : irbpp_trace_kernel_c16);
-        hipLaunchKernelGGL(trace_fn, dim3(tgrid), dim3(64), 0, st, Pt, env->S, env->phase_cycles);
+    io.use_order = plan.use_order;
+    io.heavy_turn = plan.heavy_turn;
+    io.obs_rows = plan.obs_rows == ROWS_TRACK ? rows : nullptr;
+    if (plan.obs_rows == ROWS_FORGET) hipMemsetAsync(rows, 0xFF, (size_t)env->P.N * sizeof(int32_t), st);
+    const int32_t* const actions = io.actions;
+    for (int i = 0; i < plan.n_launches; ++i) {
+        const Launch& l = plan.launch[i];
+        const void* fn = kernel_registry[l.kernel];
+        switch (l.kernel) {
+            case K_ITEM_ORDER:
+                hipLaunchKernelGGL(irbpp_item_order_kernel, dim3(l.grid), dim3(l.block), l.lds, st, env->T, env->S, n);
+                break;
+            case K_HEURISTIC: {          // HM's scorer: its triples are the cells of the apply kernel behind it (of that launch alone)
+                StepIO sel = io;
+                sel.heur_out = env->heur_cells;
+                hipLaunchKernelGGL(irbpp_heuristic_kernel, dim3(l.grid), dim3(l.block), l.lds, st, env->P, env->T, env->S, sel);
+                io.actions = env->heur_cells;
+                break;
+            }
+            case K_TRACE: case K_TRACE_C32: case K_TRACE_C16: case K_TRACE_REFILL: {
+                Params Pt = env->P;
+                if (plan.inline_polygon) Pt.round_cap = 0;
+                hipLaunchKernelGGL((trace_kernel_fn)fn, dim3(l.grid), dim3(l.block), l.lds, st, Pt, env->S, env->phase_cycles);
+                break;
+            }
+            case K_POLYGON:
 #ifdef IRBPP_AB_POLY_ACCOUNT
-        if (!inline_polygon) hipLaunchKernelGGL(irbpp_polygon_kernel, dim3(pgrid), dim3(64), 0, st, env->P, env->S, env->phase_cycles);
+                hipLaunchKernelGGL(irbpp_polygon_kernel, dim3(l.grid), dim3(l.block), l.lds, st, env->P, env->S, env->phase_cycles);
 #else
-        if (!inline_polygon) hipLaunchKernelGGL(irbpp_polygon_kernel, dim3(pgrid), dim3(64), 0, st, env->P, env->S);
+                hipLaunchKernelGGL(irbpp_polygon_kernel, dim3(l.grid), dim3(l.block), l.lds, st, env->P, env->S);
 #endif
-        // lattice and box data (practically never more than S candidates per bin): a wave per bin, four bins per workgroup
-        // -- from 2048 bins on: a launch over 1024 bins is one such workgroup per CU, 2.6 % slower than a workgroup per bin (profiles/r05/s7)
-        const bool wave_emit = lattice_images(env->P) && !heavy_first && !(env->cfg.tuning & IRBPP_TUNE_BLOCK_EMIT) &&
-                               (n >= 2048 || (env->cfg.tuning & IRBPP_TUNE_WAVE_EMIT));
-        env_kernel_fn emit_fn = wave_emit ? irbpp_emit_wave_kernel : irbpp_emit_kernel;
-#if !defined(IRBPP_NO_SPEC) && !defined(IRBPP_ABLATE)
-        switch (pick_spec(env)) {
-            case 1: emit_fn = wave_emit ? irbpp_emit_wave_kernel_s1 : irbpp_emit_kernel_s1; break;
-            case 2: emit_fn = wave_emit ? irbpp_emit_wave_kernel_s2 : irbpp_emit_kernel_s2; break;
-            case 3: emit_fn = irbpp_emit_kernel_s3; break;
-            case 4: emit_fn = irbpp_emit_kernel_s4; break;
-            case 5: emit_fn = wave_emit ? irbpp_emit_wave_kernel_s5 : irbpp_emit_kernel_s5; break;
-            default: break;
+                break;
+            default:
+                hipLaunchKernelGGL((env_kernel_fn)fn, dim3(l.grid), dim3(l.block), l.lds == LDS_WIDE_LAYOUT ? wide_layout(env->P).bytes : l.lds,
+                                   st, env->P, env->T, env->S, io, l.mode);
+                io.actions = actions;
         }
-#endif
-        const int egrid = wave_emit ? (n + 3) / 4 : n + (heavy_first ? env->P.heavy_cap : 0);
-        hipLaunchKernelGGL(emit_fn, dim3(egrid), dim3(256), env->P.emit_lds_bytes, st, env->P, env->T, env->S, io, mode);
     }
 }
 
@@ -833,13 +603,18 @@ static bool graph_wanted(const irbpp_env* env, int) { return (env->cfg.tuning & 
 
 static int launch_env(irbpp_env* env, StepIO io, int mode, void* stream, int grid = 0, int key = KEY_CAND) {
     if (grid <= 0) grid = env->P.N;
-    if (key == KEY_HEUR && grid != env->P.N) return IRBPP_ERR_ARG;     // (HM's scorer covers all bins: launch_apply)
+    if (key == KEY_HEUR && grid != env->P.N) return IRBPP_ERR_ARG;     // (HM's scorer covers all bins: plan_transition)
     io.phase_cycles = env->phase_cycles;
     hipStream_t st = (hipStream_t)stream;
     size_t pairs = env->timing.size() / 2;
     const size_t slot = env->timing_next;
     if (pairs && (env->timing_phase++ % env->timing_every) != 0) pairs = 0;       // not a sampled launch
     if (pairs) hipEventRecord(env->timing[2 * slot], st);
+    int32_t* rows = nullptr;               // the row counts of io.obs, if it is a registered observation buffer
+    for (auto& rb : env->obs_buffers)
+        if (io.obs != nullptr && rb.first == io.obs) rows = rb.second;
+    const Plan plan = plan_transition(env->P, env->cfg.tuning, mode, grid, key == KEY_HEUR && io.heur_method == 4 ? PLAN_KEY_HEUR_HM : key,
+                                      io.bin_list != nullptr, rows != nullptr, env->heavy_turn, env->item_order);
     bool launched = false;
     if (graph_wanted(env, grid) && (mode == MODE_STEP || mode == MODE_CANDS) && key == KEY_CAND) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -865,12 +640,11 @@ static int launch_env(irbpp_env* env, StepIO io, int mode, void* stream, int gri
                 env->graphs.push_back({std::vector<uint8_t>(kb, kb + sizeof k), nullptr, nullptr, ++env->graph_clock});
             } else {
                 hit->used = ++env->graph_clock;
-                const int turn_before = env->heavy_turn;
                 if (hit->exec == nullptr) {              // second sight: capture the chain on the library's own stream
                     if (env->cap_stream == nullptr && hipStreamCreateWithFlags(&env->cap_stream, hipStreamNonBlocking) != hipSuccess)
                         env->cap_stream = nullptr;
                     if (env->cap_stream != nullptr && hipStreamBeginCapture(env->cap_stream, hipStreamCaptureModeRelaxed) == hipSuccess) {
-                        launch_group(env, io, mode, env->cap_stream, 0, grid);
+                        launch_group(env, io, plan, rows, env->cap_stream, grid);
                         hipGraph_t graph = nullptr;
                         if (hipStreamEndCapture(env->cap_stream, &graph) == hipSuccess && graph != nullptr &&
                             hipGraphInstantiate(&hit->exec, graph, nullptr, nullptr, 0) == hipSuccess) {
@@ -879,23 +653,18 @@ static int launch_env(irbpp_env* env, StepIO io, int mode, void* stream, int gri
                             if (graph) hipGraphDestroy(graph);
                             hit->exec = nullptr;
                         }
-                        env->heavy_turn = turn_before;   // (the capture ran the host code of a launch; the launch itself follows)
                         (void)hipGetLastError();
                     }
                 }
                 if (hit->exec != nullptr && hipGraphLaunch(hit->exec, st) == hipSuccess) {
                     launched = true;
                     ++env->graph_replays;
-                    // the host-side state a direct launch would have advanced
-                    const bool observes = mode == MODE_CANDS || (mode == MODE_STEP && env->P.K == 1);
-                    const bool heavy_first = env->P.split && observes && env->P.heavy_cap > 0 && !lattice_images(env->P) &&
-                                             io.bin_list == nullptr && !(env->cfg.tuning & IRBPP_TUNE_NO_HEAVY_FIRST);
-                    if (heavy_first) env->heavy_turn ^= 1;
                 }
             }
         }
     }
-    if (!launched) launch_group(env, io, mode, st, 0, grid, key);
+    if (!launched) launch_group(env, io, plan, rows, st, grid);
+    if (plan.heavy_first) env->heavy_turn ^= 1;      // (the one place it advances: behind a transition that went out, replayed or direct)
     if (pairs) {
         hipEventRecord(env->timing[2 * slot + 1], st);
         env->timing_next = (slot + 1) % pairs;
@@ -992,7 +761,7 @@ int irbpp_step(irbpp_env* env, const int32_t* actions_dev, float* obs_dev, const
 // a step whose placement does not come from a candidate row is always the apply kernel + MODE_OBSERVE: configurations that
 // apply inside the transition kernel cannot take it
 static bool applies_in_transition(const irbpp_env* env) {
-    return env->P.stability != 0 || (env->cfg.tuning & IRBPP_TUNE_FUSED_APPLY) || chain_launch(env, env->P.N);
+    return env->P.stability != 0 || (env->cfg.tuning & IRBPP_TUNE_FUSED_APPLY) || chain_launch(env->P, env->cfg.tuning);
 }
 
 int irbpp_step_cells(irbpp_env* env, const int32_t* cells_dev, float* obs_dev, const irbpp_step_out* out, void* stream) {
@@ -1368,32 +1137,38 @@ int irbpp_debug_phase_cycles(irbpp_env* env, int64_t* cycles_dev) {
 
 int irbpp_debug_kernel_info(const irbpp_env* env, int32_t* lds_bytes, const char** kernel_name) {
     if (!env || !lds_bytes || !kernel_name) return IRBPP_ERR_ARG;
-    *lds_bytes = env->P.lds_bytes;
-    // the kernels of a step over all bins of this environment, in launch order behind the transition kernel's build
-    const int n = env->P.N, spec = pick_spec(env);
-    const bool lattice = lattice_images(env->P);
-    const bool wave_emit = lattice && !(env->cfg.tuning & IRBPP_TUNE_BLOCK_EMIT) && (n >= 2048 || (env->cfg.tuning & IRBPP_TUNE_WAVE_EMIT));
-    const int cpw = pick_trace_cpw(env, n);
-    char emit[48];
-    snprintf(emit, sizeof emit, "%s%s", wave_emit ? "irbpp_emit_wave_kernel" : "irbpp_emit_kernel",
-             spec == 1 ? "_s1" : spec == 2 ? "_s2" : (spec == 3 && !wave_emit) ? "_s3" : (spec == 4 && !wave_emit) ? "_s4" : spec == 5 ? "_s5" : "");
-    snprintf(const_cast<irbpp_env*>(env)->kernel_names, sizeof env->kernel_names, "%s + irbpp_trace_kernel%s + irbpp_polygon_kernel + %s%s",
-             pick_env_kernel(env).name, cpw > 64 ? "_refill" : cpw == 64 ? "" : (cpw == 32 ? "_c32" : "_c16"), emit,
-             !split_apply(env, n) ? "" : (env->P.K > 1 ? (n < 2048 ? " (step: irbpp_apply_wg_kernel alone)" : " (step: irbpp_apply_kernel alone)")
-                                                       : " (step: irbpp_apply_kernel in front, transition kernel in MODE_OBSERVE)"));
-    if (env->P.wide) {
+    const Params& P = env->P;
+    *lds_bytes = P.lds_bytes;
+    // the plan of a step over all bins of this environment, rendered: the kernels of its observation in launch order (a buffered
+    // step observes nothing: the plan of the get_action_candidates behind it), then where the step's actions are applied
+    const Plan step = plan_transition(P, env->cfg.tuning, MODE_STEP, P.N, PLAN_KEY_CAND, false, false, env->heavy_turn, env->item_order);
+    const Plan obs = P.K > 1 ? plan_transition(P, env->cfg.tuning, MODE_CANDS, P.N, PLAN_KEY_CAND, false, false, env->heavy_turn, false) : step;
+    std::string text;
+    int shown = 0, last = -1, apply = -1;
+    for (int i = 0; i < obs.n_launches; ++i) {
+        const int k = obs.launch[i].kernel;
+        if (is_apply_kernel(k) || k == K_ITEM_ORDER) continue;
+        text += shown++ ? " + " : "";
+        text += kernel_info(last = k).name;
+    }
+    for (int i = 0; i < step.n_launches; ++i)
+        if (is_apply_kernel(step.launch[i].kernel)) apply = step.launch[i].kernel;
+    const bool alone = apply >= 0 && step.launch[step.n_launches - 1].kernel == apply;
+    const std::string applied = apply >= 0 ? kernel_info(apply).name : "";
+    if (shown == 1 && last == K_WIDE) {
         // (what sends the configuration there: the grid, and / or more height levels than the tuned pipeline codes)
-        const int levels = (int)floor(env->P.bin_z / env->P.res_z + 1e-9);
-        char why[48] = "";
-        if (levels > TUNED_MAX_LEVELS) snprintf(why, sizeof why, ", %d height levels", levels);
-        snprintf(const_cast<irbpp_env*>(env)->kernel_names, sizeof env->kernel_names, "irbpp_wide_kernel alone (action grid of %d x %d cells%s)%s", env->P.Ax,
-                 env->P.Ay, why, env->P.K > 1 ? " (step: the apply kernel alone)" : " (step: irbpp_apply_kernel in front)");
+        const int levels = (int)floor(P.bin_z / P.res_z + 1e-9);
+        text += " alone (action grid of " + std::to_string(P.Ax) + " x " + std::to_string(P.Ay) + " cells";
+        if (levels > TUNED_MAX_LEVELS) text += ", " + std::to_string(levels) + " height levels";
+        text += ")";
+        if (alone) text += " (step: the apply kernel alone)";
+        else if (apply >= 0) text += " (step: " + applied + " in front)";
+    } else {
+        if (shown == 1) text += " alone (observation finished in the bin's workgroup)";
+        if (alone) text += " (step: " + applied + " alone)";
+        else if (apply >= 0) text += " (step: " + applied + " in front, transition kernel in MODE_OBSERVE)";
     }
-    else if (chain_launch(env, n)) {
-        const bool s1 = spec == 1;
-        snprintf(const_cast<irbpp_env*>(env)->kernel_names, sizeof env->kernel_names, "%s alone (observation finished in the bin's workgroup)%s",
-                 s1 ? "irbpp_env_kernel_chain_s1" : "irbpp_env_kernel_chain", env->P.K > 1 ? " (step: irbpp_apply_wg_kernel alone)" : "");
-    }
+    snprintf(const_cast<irbpp_env*>(env)->kernel_names, sizeof env->kernel_names, "%s", text.c_str());
     *kernel_name = env->kernel_names;
     return IRBPP_OK;
 }

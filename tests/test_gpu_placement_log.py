@@ -358,8 +358,8 @@ def test_wide_step_cells_log_has_refused_entries_beyond_cell_15():
 
 # -- e. the launch forms: a wave per bin, the apply kernel in front, the chain build -------------------------------------------------
 @pytest.mark.parametrize("k,n,tuning,kernel", [
-    (3, 2048, 0, "irbpp_apply_kernel alone"),                   # buffered: a wave per bin from 2048 bins on (launch_apply)
-    (1, 4096, 0, "irbpp_apply_kernel in front"),                # online, lattice data: split from 4096 bins on (split_apply)
+    (3, 2048, 0, "irbpp_apply_kernel alone"),                   # buffered: a wave per bin from 2048 bins on (irbpp_plan.h: plan_transition)
+    (1, 4096, 0, "irbpp_apply_kernel in front"),                # online, lattice data: split from 4096 bins on (irbpp_plan.h: split_apply)
     (1, 3, _lib.TUNE_CHAIN, "irbpp_env_kernel_chain"),          # the chain build accepts any size
     (3, 3, _lib.TUNE_CHAIN, "irbpp_apply_wg_kernel alone")])
 def test_every_bin_of_a_launch_form_logs_the_same_episode(k, n, tuning, kernel):
