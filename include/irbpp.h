@@ -398,6 +398,14 @@ typedef struct {
  * ep_reward_dev, ratio_dev or counter_dev is IRBPP_ERR_ARG.  Works with IRBPP_TUNE_GRAPH (the launch follows the replayed
  * graph).  Detached, a step launches exactly what it launched before.  The buffers must outlive the attachment. */
 int irbpp_set_episode_window(irbpp_env* env, const irbpp_episode_window* window);
+/* One step of a window without an environment: appends the bins whose done_dev[b] != 0 (bin order, global bin =
+ * global_offset + b) and writes the snapshot of the step, exactly as a windowed irbpp_step does behind its kernels (which
+ * calls this function: it is the only launch of the update kernel).  done_dev uint8[n_bins], ep_reward_dev / ratio_dev
+ * float64[n_bins], counter_dev int32[n_bins].  IRBPP_ERR_ARG for a NULL pointer, a window irbpp_set_episode_window would
+ * refuse, or n_bins < 1.  Asynchronous on `stream`. */
+int irbpp_episode_window_update(const irbpp_episode_window* window, const uint8_t* done_dev, const double* ep_reward_dev,
+                                const double* ratio_dev, const int32_t* counter_dev, int32_t n_bins, int32_t global_offset,
+                                void* stream);
 /* The rows the trainer logs (trainer.py:215-222) for steps first_step .. first_step + n_steps - 1 of n_parts windows whose
  * bins together are the trainer's envs (groups of bins, ranks: any order; the global bin index orders them).  out_dev:
  * float64[n_steps][7] = (T, n, mean r, max r, min r, mean ratio, mean counter), n = len(deque) and the five statistics NaN

@@ -99,6 +99,8 @@ SIGNATURES = {
     "irbpp_episode_totals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "irbpp_set_placement_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "irbpp_set_episode_window": (C.c_int, [C.c_void_p, C.POINTER(IrbppEpisodeWindow)]),
+    "irbpp_episode_window_update": (C.c_int, [C.POINTER(IrbppEpisodeWindow), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                              C.c_int32, C.c_void_p]),
     "irbpp_episode_metrics": (C.c_int, [C.POINTER(IrbppEpisodeWindow), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "irbpp_sumtree_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

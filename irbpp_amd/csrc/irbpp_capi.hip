@@ -745,11 +745,8 @@ static int step_common(irbpp_env* env, const int32_t* actions_dev, float* obs_de
     const int rc = launch_env(env, io, MODE_STEP, stream, 0, key);
     if (rc != IRBPP_OK || !windowed) return rc;
     // the episode window (irbpp_metrics.hip): one workgroup behind the step's kernels, reading the outputs they wrote
-    const irbpp_episode_window& w = env->window;
-    hipLaunchKernelGGL(irbpp_window_update_kernel, dim3(1), dim3(WINDOW_UPDATE_THREADS), 0, (hipStream_t)stream, out->done_dev,
-                       out->ep_reward_dev, out->ratio_dev, out->counter_dev, env->P.N, env->cfg.global_offset, w.ring_dev,
-                       w.snapshot_dev, w.rows_dev, w.state_dev, w.window, w.history);
-    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+    return irbpp_episode_window_update(&env->window, out->done_dev, out->ep_reward_dev, out->ratio_dev, out->counter_dev, env->P.N,
+                                       env->cfg.global_offset, stream);
 }
 
 int irbpp_step(irbpp_env* env, const int32_t* actions_dev, float* obs_dev, const irbpp_step_out* out, void* stream) {
@@ -947,14 +944,28 @@ int irbpp_set_placement_log(irbpp_env* env, uint32_t* meta_dev, double* z_dev, i
     return IRBPP_OK;
 }
 
+static bool window_ok(const irbpp_episode_window* w) {
+    return w->ring_dev && w->snapshot_dev && w->rows_dev && w->state_dev && w->window >= 1 && w->window <= WINDOW_MAX &&
+           w->history >= 1;
+}
+
 int irbpp_set_episode_window(irbpp_env* env, const irbpp_episode_window* w) {
     if (!env) return IRBPP_ERR_ARG;
     if (w == nullptr) { env->window = irbpp_episode_window{}; return IRBPP_OK; }
-    if (!w->ring_dev || !w->snapshot_dev || !w->rows_dev || !w->state_dev || w->window < 1 || w->window > WINDOW_MAX ||
-        w->history < 1)
-        return IRBPP_ERR_ARG;
+    if (!window_ok(w)) return IRBPP_ERR_ARG;
     env->window = *w;
     return IRBPP_OK;
+}
+
+// the one launch site of the update kernel: a windowed step (step_common) ends here too
+int irbpp_episode_window_update(const irbpp_episode_window* w, const uint8_t* done_dev, const double* ep_reward_dev,
+                                const double* ratio_dev, const int32_t* counter_dev, int32_t n_bins, int32_t global_offset,
+                                void* stream) {
+    if (!w || !done_dev || !ep_reward_dev || !ratio_dev || !counter_dev || !window_ok(w) || n_bins < 1) return IRBPP_ERR_ARG;
+    hipLaunchKernelGGL(irbpp_window_update_kernel, dim3(1), dim3(WINDOW_UPDATE_THREADS), 0, (hipStream_t)stream, done_dev,
+                       ep_reward_dev, ratio_dev, counter_dev, n_bins, global_offset, w->ring_dev, w->snapshot_dev, w->rows_dev,
+                       w->state_dev, w->window, w->history);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
 }
 
 int irbpp_episode_metrics(const irbpp_episode_window* parts, int32_t n_parts, int32_t first_step, int32_t n_steps,

@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from episode_window_model import halfway_cases
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "host", "metrics_host.cpp")
 OUT = os.path.join(HERE, "host", "_build", "libmetrics_host.so")
@@ -57,15 +59,7 @@ def test_round6_is_pythons_round_on_random_values(host):
 
 
 def test_round6_on_constructed_halfway_cases(host):
-    k = np.arange(-20000, 20000, dtype=np.float64)
-    exact_ties = (2 * k + 1) / 128.0                    # seven decimals ending in 5, exact in binary: true ties, half to even
-    near = (k + 0.5) / 1e6                              # p = x * 1e6 rounds to (or next to) a half-integer
-    around = [np.nextafter(near, np.inf), np.nextafter(near, -np.inf),
-              np.nextafter(np.nextafter(near, np.inf), np.inf), np.nextafter(np.nextafter(near, -np.inf), -np.inf)]
-    # x whose rounded product is exactly k + 0.5 while the exact product is not: every ulp step of x around (k+0.5)/1e6
-    steps = [near * (1 + d * 2.0 ** -52) for d in range(-3, 4)]
-    x = np.concatenate([exact_ties, -exact_ties, near, -near] + around + steps + [np.array([0.0, -0.0, 5e-7, -5e-7, 1.5e-6,
-                                                                                              2.5e-6, 1e-300, -1e-300])])
+    x, exact_ties, near = halfway_cases()
     got, want = _round6(host, x), _python_round(x)
     assert _bits_equal(got, want), x[np.nonzero(got.view(np.int64) != want.view(np.int64))[0][:5]]
     lo = 2 * exact_ties.size

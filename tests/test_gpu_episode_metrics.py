@@ -5,7 +5,6 @@ import ctypes as C
 import os
 import subprocess
 import sys
-from collections import deque
 
 import numpy as np
 import pytest
@@ -15,48 +14,12 @@ import irbpp_amd  # noqa: F401
 from irbpp_amd import _lib
 from irbpp_amd.metrics import EpisodeMetrics, EpisodeMetricsOverrun
 from irbpp_amd.vec_env import GpuPackingEnv, GroupedPackingEnv, _Infos
+from episode_window_model import assert_rows_equal, trainer_rows
 from helpers import _bench_workload
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def trainer_rows(steps, W):
-    """trainer.py:145-147, 168-178, 215-222 over (done, infos) per step: one row per step, NaN where nothing is logged."""
-    episode_rewards = deque(maxlen=W)
-    episode_ratio = deque(maxlen=W)
-    episode_counter = deque(maxlen=W)
-    rows = []
-    for T, (done, infos) in enumerate(steps, start=1):
-        for _ in range(len(infos)):
-            if done[_] and infos[_]['Valid']:
-                if 'reward' in infos[_].keys():
-                    episode_rewards.append(infos[_]['reward'])
-                else:
-                    episode_rewards.append(infos[_]['episode']['r'])
-                if 'ratio' in infos[_].keys():
-                    episode_ratio.append(infos[_]['ratio'])
-                if 'counter' in infos[_].keys():
-                    episode_counter.append(infos[_]['counter'])
-        row = [T, len(episode_rewards)] + [np.nan] * 5
-        if len(episode_rewards) != 0:
-            row[2:5] = np.mean(episode_rewards), np.max(episode_rewards), np.min(episode_rewards)
-        if len(episode_ratio) != 0:
-            row[5] = np.mean(episode_ratio)
-        if len(episode_counter) != 0:
-            row[6] = np.mean(episode_counter)
-        rows.append(row)
-    return np.array(rows, dtype=np.float64)
-
-
-def assert_rows_equal(got, want):
-    assert got.shape == want.shape, (got.shape, want.shape)
-    nan_g, nan_w = np.isnan(got), np.isnan(want)
-    np.testing.assert_array_equal(nan_g, nan_w)
-    g, w = np.where(nan_g, 0.0, got), np.where(nan_w, 0.0, want)
-    bad = np.nonzero(g.view(np.int64) != w.view(np.int64))
-    assert bad[0].size == 0, f"first differing row {got[bad[0][0]]} vs {want[bad[0][0]]}"
 
 
 def _play(env, metrics, steps, read_every=50, buffered=False, host_infos=True):
@@ -89,6 +52,23 @@ def test_rows_equal_the_trainer_loop(workload, extra):
         rows, host = _play(env, m, 200)
         want = trainer_rows(host, W)
         assert rows.shape[0] == 200 and np.array_equal(rows[:, 0], np.arange(1, 201))
+        assert want[-1, 1] == min(W, sum(int(d.sum()) for d, _ in host)) and want[-1, 1] > 0
+        assert_rows_equal(rows, want)
+        m.close()
+    env.check_device_error()
+    env.close()
+
+
+def test_rows_equal_the_trainer_loop_beyond_a_workgroup_of_bins():
+    """2560 bins: every thread of the update kernel's one workgroup owns a segment of three bins (seg = 3), 854 threads hold
+    bins (the last of them one bin only) and 170 none."""
+    shapes, seqs, kw = _bench_workload("blockout")
+    env = GpuPackingEnv(shapes, seqs, 2560, device=DEV, **kw)
+    for W in (10, 1000):
+        m = EpisodeMetrics(env, window=W, history=64)
+        rows, host = _play(env, m, 120)
+        want = trainer_rows(host, W)
+        assert rows.shape[0] == 120 and np.array_equal(rows[:, 0], np.arange(1, 121))
         assert want[-1, 1] == min(W, sum(int(d.sum()) for d, _ in host)) and want[-1, 1] > 0
         assert_rows_equal(rows, want)
         m.close()
