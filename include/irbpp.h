@@ -434,6 +434,63 @@ int irbpp_episode_metrics(const irbpp_episode_window* parts, int32_t n_parts, in
  * reported done.  NULL, NULL switches the log off; one NULL pointer of the two is IRBPP_ERR_ARG. */
 int irbpp_set_placement_log(irbpp_env* env, uint32_t* meta_dev, double* z_dev, int32_t capacity);
 
+/* Save, restore and fork bins on the device.
+ *
+ * The state of a bin is the set of per-bin rows a later call on that bin reads and an earlier call on it wrote (the segment table of
+ * csrc/irbpp_binstate.h): heightmap, item queue, candidate keys of the last observation, the bin's line of
+ * scalars (cursor, episode count, trajectory row of the running episode, counters and sums), the drop-height and naiveMask grids of
+ * the last observation, the placement-log rows when a log is attached, and -- for save / load only -- the bin's share of
+ * irbpp_episode_totals.  A per-bin blob holds these rows back to back, each padded to 16 bytes: bytes_per_bin bytes.
+ *
+ *   irbpp_bin_blob_info_get   what a blob of this environment is: layout version, bytes per bin, and the two keys a blob (or a second
+ *                             environment) must share with an environment to be loaded into (copied to) it.  num_bins, global_offset
+ *                             and global_bins take no part in the keys: a search environment of N * B bins beside a root environment
+ *                             of N bins is the intended use.  A placement log's capacity is part of geometry_key (a blob saved
+ *                             with a log loads only into an environment with a log of that capacity).  IRBPP_ERR_STATE before
+ *                             both tables are loaded.
+ *   irbpp_save_bins           blob row i = the state of bin bins_dev[i]; blob_dev: count * bytes_per_bin bytes, 16-byte aligned.
+ *   irbpp_load_bins           bin bins_dev[i] = blob row i: the bin is what it was at the save, its totals included.  `info` is the
+ *                             info the blob was saved with: IRBPP_ERR_ARG if its version, bytes_per_bin, geometry_key or tables_key
+ *                             differ from the environment's own.
+ *   irbpp_copy_bins           bin dst_bins_dev[i] of dst = bin src_bins_dev[i] of src (src may be dst).  After it the destination bin
+ *                             behaves exactly as its source would, call for call, until the running episode ends: it draws the
+ *                             items its source would draw (the episode's trajectory row travels).  The NEXT episode is the
+ *                             destination's own: the trajectory row of its own index with the copied episode count.  The
+ *                             destination's totals are untouched (a finished episode is not counted twice); the placement-log rows
+ *                             of the running episode are copied.  IRBPP_ERR_ARG if the two environments differ in a key, are on
+ *                             different devices, or one has a placement log and the other none.
+ *
+ * bins_dev: int32[count] local bin indices in device memory.  An index outside [0, num_bins) makes its pair a no-op and raises
+ * IRBPP_DEVERR_BAD_BIN in the sticky error word of the destination environment (irbpp_save_bins: of env); the other pairs are served.
+ * OVERLAP IS THE CALLER'S CONTRACT: within one call the destination bins are pairwise distinct, and with src == dst no bin is both
+ * a source and a destination unless it is paired with itself (a no-op).  The library does not check this on the device; the Python
+ * wrappers do (vec_env.GpuPackingEnv.fork_bins).
+ * count == 0 is IRBPP_OK (answered first, after the NULL / negative-count checks); IRBPP_ERR_STATE before irbpp_reset.
+ * Item-stream environments (item_stream = 1) answer IRBPP_ERR_ARG from all three calls: a ring row belongs to its bin AND to a feeder
+ * that counts what it delivered, so copying one is a design of its own.  The stability proxy keeps nothing per bin: allowed.
+ * Host-side flags: the destination's "stored grids are current" flag stays set only if the source's (the blob's grids_current) is set
+ * too, otherwise irbpp_heuristic_step answers IRBPP_ERR_STATE until the next observation of all bins, as after
+ * irbpp_set_heightmaps.  Registered observation buffers are the caller's memory and are not touched: a caller that copies
+ * observation rows itself calls irbpp_invalidate_obs_buffer.  Replayed graphs (IRBPP_TUNE_GRAPH), the error word handed to
+ * irbpp_step and an attached episode window are left as they are (a window belongs to an environment's step stream, not to a bin).
+ * Asynchronous on `stream`, which must follow the steps of both environments. */
+typedef struct irbpp_bin_blob_info {
+    int32_t version;          /* layout version of the segment table, starts at 1 */
+    int32_t bytes_per_bin;    /* multiple of 16 */
+    uint64_t geometry_key;    /* hash of every Params field the table and the kernels' reading of it depend on:
+                                 Hx, Hy, Ax, Ay, step, R, S, K, resolutions, bin size, wide, log capacity */
+    uint64_t tables_key;      /* hash of what irbpp_load_shapes and irbpp_load_sequences were given */
+    int32_t grids_current;    /* the environment's flag when the blob was written */
+    int32_t reserved;
+} irbpp_bin_blob_info;
+
+int irbpp_bin_blob_info_get(const irbpp_env* env, irbpp_bin_blob_info* out);
+int irbpp_save_bins(irbpp_env* env, const int32_t* bins_dev, int32_t count, void* blob_dev, void* stream);
+int irbpp_load_bins(irbpp_env* env, const irbpp_bin_blob_info* info, const int32_t* bins_dev, int32_t count,
+                    const void* blob_dev, void* stream);
+int irbpp_copy_bins(irbpp_env* dst, const int32_t* dst_bins_dev, irbpp_env* src, const int32_t* src_bins_dev,
+                    int32_t count, void* stream);
+
 /* Caller side: the N per-env prioritised replay memories of main.py:61-63 as one tensor set.
  * replaces: SegmentTree.find/_retrieve (memory.py:72-86) for `draws` values per env.
  * tree_dev float32[n_env][2*capacity-1] (implicit heap, leaves at capacity-1..), values_dev float32[n_env][draws];
@@ -576,7 +633,8 @@ int irbpp_device_error(irbpp_env* env, void* stream, int32_t* flags_out);
 #define IRBPP_DEVERR_LEVEL_RANGE   1   /* a height level fell outside the level codes of the configuration */
 #define IRBPP_DEVERR_TRACE_GUARD   2   /* border following exceeded its iteration guard      */
 #define IRBPP_DEVERR_BAD_ITEM      4   /* item id outside the loaded shape table             */
-#define IRBPP_DEVERR_BAD_BIN       8   /* irbpp_reset_bins: bin index outside [0, num_bins)  */
+#define IRBPP_DEVERR_BAD_BIN       8   /* irbpp_reset_bins, irbpp_save_bins / irbpp_load_bins / irbpp_copy_bins: bin index outside
+                                          [0, num_bins); the bin (the pair) was skipped              */
 #define IRBPP_DEVERR_CAPACITY     16   /* a die's candidate list overflowed (it holds twice the worst case of a fair
                                           share of the bins): results of that step are incomplete                */
 #define IRBPP_DEVERR_BAD_ACTION   64   /* irbpp_step / irbpp_get_action_candidates: an action outside [-S, S) (order action: [-k, k)):

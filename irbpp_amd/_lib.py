@@ -47,6 +47,11 @@ class IrbppEpisodeWindow(C.Structure):
                 ("window", C.c_int32), ("history", C.c_int32)]
 
 
+class IrbppBinBlobInfo(C.Structure):
+    _fields_ = [("version", C.c_int32), ("bytes_per_bin", C.c_int32), ("geometry_key", C.c_uint64), ("tables_key", C.c_uint64),
+                ("grids_current", C.c_int32), ("reserved", C.c_int32)]
+
+
 class IrbppStepOut(C.Structure):
     _fields_ = [("reward_dev", C.c_void_p), ("done_dev", C.c_void_p), ("counter_dev", C.c_void_p),
                 ("ratio_dev", C.c_void_p), ("ep_reward_dev", C.c_void_p), ("ep_len_dev", C.c_void_p),
@@ -98,6 +103,10 @@ SIGNATURES = {
     "irbpp_set_heightmaps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "irbpp_episode_totals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "irbpp_set_placement_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "irbpp_bin_blob_info_get": (C.c_int, [C.c_void_p, C.POINTER(IrbppBinBlobInfo)]),
+    "irbpp_save_bins": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "irbpp_load_bins": (C.c_int, [C.c_void_p, C.POINTER(IrbppBinBlobInfo), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "irbpp_copy_bins": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "irbpp_set_episode_window": (C.c_int, [C.c_void_p, C.POINTER(IrbppEpisodeWindow)]),
     "irbpp_episode_window_update": (C.c_int, [C.POINTER(IrbppEpisodeWindow), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                               C.c_int32, C.c_void_p]),

@@ -27,6 +27,7 @@
 #include "irbpp_metrics.hip"        // the trainer's episode metrics (irbpp_set_episode_window)
 #include "irbpp_itemgen.h"
 #include "irbpp_plan.h"             // which kernels a transition launches: the registry of kernels and plan_transition
+#include "irbpp_binstate.hip"       // save, restore and fork bins (irbpp_save_bins, irbpp_load_bins, irbpp_copy_bins) by irbpp_binstate.h's table
 
 using namespace irbpp;
 
@@ -57,6 +58,7 @@ struct irbpp_env {
     irbpp_episode_window window{};         // irbpp_set_episode_window (window.window == 0: none attached)
     int32_t* heur_cells = nullptr;         // [N][3] irbpp_heuristic_step: the cells a scorer kernel chose, read by irbpp_apply_cells_kernel
     bool grids_current = false;            // w_posz / w_valid of EVERY bin are those of the item its next step places, on its present heightmap
+    uint64_t shapes_key = 0, seq_key = 0;  // FNV-1a of what irbpp_load_shapes / irbpp_load_sequences were given (irbpp_bin_blob_info::tables_key)
 };
 
 #define HIP_TRY(expr)                                   \
@@ -281,6 +283,7 @@ int irbpp_load_shapes(irbpp_env* env, int32_t n_shapes, const double* extents, c
         const int64_t fx = dims[i * 2], fy = dims[i * 2 + 1];
         if (fx < 1 || fy < 1 || fx > 4096 || fy > 4096 || offsets[i] < 0 || offsets[i] + fx * fy > pool_len) return IRBPP_ERR_ARG;
     }
+    env->shapes_key = bin_shapes_key(n_shapes, R, extents, volumes, dims, offsets, pool_len, height_top, height_bottom, mask_top, mask_bottom);
     // Block path: the largest b (multiple of step, <= 8) such that every footprint of the dataset is a
     // union of b x b tiles that are fully masked out or fully masked in with one bottom height -- decided per ROTATION:
     // if every rotation qualifies the data set is pure lattice data (BlockOut at R = 4); if only some do (BlockOut at the
@@ -479,6 +482,7 @@ int irbpp_load_sequences(irbpp_env* env, const int32_t* ids, int32_t n_traj, int
     env->T.n_traj = n_traj;
     env->T.seq_len = length;
     env->T.stream = env->cfg.item_stream ? 1 : 0;
+    env->seq_key = bin_sequences_key(ids, n_traj, length);
     env->seq_loaded = true;
     return IRBPP_OK;
 }
@@ -927,6 +931,80 @@ int irbpp_set_heightmaps(irbpp_env* env, const double* hm_dev, void* stream) {
     HIP_TRY(hipMemsetAsync(env->S.w_valid, 0, (size_t)env->P.N * env->P.R * env->P.vrow * sizeof(uint32_t), (hipStream_t)stream));
     env->grids_current = false;            // (irbpp_heuristic_step answers IRBPP_ERR_STATE until the next observation of all bins)
     return IRBPP_OK;
+}
+
+// ---- save, restore and fork bins (irbpp_binstate.h: the segment table; irbpp_binstate.hip: the kernel) ----
+static void bin_blob_info_of(const irbpp_env* env, irbpp_bin_blob_info* out) {
+    memset(out, 0, sizeof *out);
+    out->version = BIN_BLOB_VERSION;
+    out->bytes_per_bin = bin_segments(env->P, env->S.log_cap).bytes_per_bin;
+    out->geometry_key = bin_geometry_key(env->P, env->S.log_cap);
+    out->tables_key = bin_tables_key(env->shapes_key, env->seq_key);
+    out->grids_current = env->grids_current ? 1 : 0;
+}
+
+extern "C++" {
+template <int MODE>
+static int launch_binstate(const irbpp_env* src, const irbpp_env* dst, const int32_t* src_bins, const int32_t* dst_bins, void* blob,
+                           int32_t count, void* stream) {
+    HIP_TRY(hipSetDevice(dst->cfg.device));
+    hipLaunchKernelGGL(irbpp_binstate_kernel<MODE>, dim3((unsigned)count), dim3(BINSTATE_THREADS), 0, (hipStream_t)stream,
+                       bin_segments(dst->P, dst->S.log_cap), src->S, dst->S, src_bins, dst_bins, (uint8_t*)blob, src->P.N, dst->P.N,
+                       src == dst ? 1 : 0);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+}  // extern "C++"
+
+int irbpp_bin_blob_info_get(const irbpp_env* env, irbpp_bin_blob_info* out) {
+    if (!env || !out) return IRBPP_ERR_ARG;
+    if (!env->shapes_loaded || !env->seq_loaded) return IRBPP_ERR_STATE;
+    bin_blob_info_of(env, out);
+    return IRBPP_OK;
+}
+
+int irbpp_save_bins(irbpp_env* env, const int32_t* bins_dev, int32_t count, void* blob_dev, void* stream) {
+    if (!env || count < 0 || (count > 0 && (!bins_dev || !blob_dev))) return IRBPP_ERR_ARG;
+    if (count == 0) return IRBPP_OK;                 // (answered before the environment is looked at)
+    if (env->cfg.item_stream) return IRBPP_ERR_ARG;
+    if (!env->was_reset) return IRBPP_ERR_STATE;
+    return launch_binstate<BINS_TO_BLOB>(env, env, bins_dev, nullptr, blob_dev, count, stream);
+}
+
+int irbpp_load_bins(irbpp_env* env, const irbpp_bin_blob_info* info, const int32_t* bins_dev, int32_t count, const void* blob_dev,
+                    void* stream) {
+    if (!env || !info || count < 0 || (count > 0 && (!bins_dev || !blob_dev))) return IRBPP_ERR_ARG;
+    if (count == 0) return IRBPP_OK;
+    if (env->cfg.item_stream) return IRBPP_ERR_ARG;
+    if (!env->shapes_loaded || !env->seq_loaded || !env->was_reset) return IRBPP_ERR_STATE;
+    irbpp_bin_blob_info own;
+    bin_blob_info_of(env, &own);
+    if (info->version != own.version || info->bytes_per_bin != own.bytes_per_bin || info->geometry_key != own.geometry_key ||
+        info->tables_key != own.tables_key)
+        return IRBPP_ERR_ARG;
+    const int rc = launch_binstate<BLOB_TO_BINS>(env, env, nullptr, bins_dev, const_cast<void*>(blob_dev), count, stream);
+    // the loaded bins' stored grids are as current as they were at the save; every other host-side flag stays: the graph cache (no
+    // pointer a captured node holds changes -- the setters that drop it change Params / Tables / State), err_mirror, the episode window
+    if (rc == IRBPP_OK) env->grids_current = env->grids_current && info->grids_current != 0;
+    return rc;
+}
+
+int irbpp_copy_bins(irbpp_env* dst, const int32_t* dst_bins_dev, irbpp_env* src, const int32_t* src_bins_dev, int32_t count,
+                    void* stream) {
+    if (!dst || !src || count < 0 || (count > 0 && (!dst_bins_dev || !src_bins_dev))) return IRBPP_ERR_ARG;
+    if (count == 0) return IRBPP_OK;
+    if (dst->cfg.item_stream || src->cfg.item_stream) return IRBPP_ERR_ARG;
+    if (!dst->was_reset || !src->was_reset) return IRBPP_ERR_STATE;
+    if (dst != src) {
+        irbpp_bin_blob_info a, b;
+        bin_blob_info_of(dst, &a);
+        bin_blob_info_of(src, &b);
+        if (a.geometry_key != b.geometry_key || a.tables_key != b.tables_key || dst->cfg.device != src->cfg.device ||
+            (dst->S.log_meta != nullptr) != (src->S.log_meta != nullptr))
+            return IRBPP_ERR_ARG;
+    }
+    const int rc = launch_binstate<BINS_TO_BINS>(src, dst, src_bins_dev, dst_bins_dev, nullptr, count, stream);
+    if (rc == IRBPP_OK) dst->grids_current = dst->grids_current && src->grids_current;      // (the other flags: as irbpp_load_bins)
+    return rc;
 }
 
 int irbpp_episode_totals(irbpp_env* env, double* out_dev, void* stream) {

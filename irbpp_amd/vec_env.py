@@ -1,6 +1,7 @@
 """Host-side mirror of the reference's vectorised-environment surface, backed by the HIP library.
 
     GpuPackingEnv   device-tensor API straight over the C ABI (include/irbpp.h)
+    BinBlob         saved bins (save_bins / load_bins / fork_bins: put a bin back, or continue a second bin from its state)
     GpuVecEnv       the ShmemVecEnv/VecPyTorch protocol the trainer calls
                     (wrapper/vec_env.py:29-138, wrapper/shmem_vec_env.py:20-117,
                     envs.py:142-165): num_envs, observation_space, action_space, reset(),
@@ -43,6 +44,49 @@ class Discrete(object):
 
 def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+class BinBlob(object):
+    """Saved bins (``save_bins``): ``info`` -- irbpp_bin_blob_info as a dict of ints (version, bytes_per_bin, geometry_key,
+    tables_key, grids_current) -- and ``data``, uint8[count, bytes_per_bin], row i = the state of the i-th saved bin
+    (csrc/irbpp_binstate.h says what that is).  ``extra``: what a wrapper adds on top (GpuVecEnv.save_state), plain tensors
+    and ints as well.  ``load_bins`` refuses a blob whose version or keys are not the environment's own."""
+
+    INFO_FIELDS = ("version", "bytes_per_bin", "geometry_key", "tables_key", "grids_current")
+
+    def __init__(self, info: dict, data: torch.Tensor, extra: Optional[dict] = None):
+        if data.dtype != torch.uint8 or data.dim() != 2 or data.shape[1] != int(info["bytes_per_bin"]):
+            raise ValueError("BinBlob data must be uint8[count, bytes_per_bin]")
+        self.info = {k: int(info[k]) for k in self.INFO_FIELDS}
+        self.data = data
+        self.extra = dict(extra or {})
+
+    @property
+    def count(self) -> int:
+        return int(self.data.shape[0])
+
+    def to_file(self, path) -> None:
+        """torch.save of plain tensors (on the CPU) and ints only."""
+        extra = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else int(v)) for k, v in self.extra.items()}
+        torch.save({"info": dict(self.info), "data": self.data.detach().cpu(), "extra": extra}, path)
+
+    @classmethod
+    def from_file(cls, path, device="cpu") -> "BinBlob":
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        extra = {k: (v.to(device) if isinstance(v, torch.Tensor) else int(v)) for k, v in d["extra"].items()}
+        return cls(d["info"], d["data"].to(device).contiguous(), extra)
+
+
+def _check_fork_pairs(src: np.ndarray, dst: np.ndarray, n_src: int, n_dst: int, same_env: bool) -> None:
+    """irbpp_copy_bins' overlap contract (include/irbpp.h) on host copies of the indices."""
+    if len(src) != len(dst):
+        raise ValueError("fork_bins needs as many source as destination bins")
+    if len(src) and (src.min() < 0 or src.max() >= n_src or dst.min() < 0 or dst.max() >= n_dst):
+        raise ValueError("fork_bins: bin index outside the environment")
+    if len(np.unique(dst)) != len(dst):
+        raise ValueError("fork_bins: destination bins must be pairwise distinct")
+    if same_env and np.isin(dst[src != dst], src).any():
+        raise ValueError("fork_bins: a bin is both a source and a destination")
 
 
 class GpuPackingEnv(object):
@@ -281,6 +325,83 @@ class GpuPackingEnv(object):
         out = torch.empty((4,), dtype=torch.float64, device=self.device)
         _lib.check(self.lib.irbpp_episode_totals(self._h, _ptr(out), self._stream()), "irbpp_episode_totals")
         return out
+
+    # -- save, restore and fork bins (irbpp_save_bins / irbpp_load_bins / irbpp_copy_bins) ----------
+    def _bins(self, bins) -> torch.Tensor:
+        """int32[count] on the device, contiguous"""
+        if not isinstance(bins, torch.Tensor):
+            bins = torch.from_numpy(np.asarray(bins, dtype=np.int32).reshape(-1))
+        return bins.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+
+    def bin_blob_info(self) -> dict:
+        info = _lib.IrbppBinBlobInfo()
+        _lib.check(self.lib.irbpp_bin_blob_info_get(self._h, C.byref(info)), "irbpp_bin_blob_info_get")
+        return {k: int(getattr(info, k)) for k in BinBlob.INFO_FIELDS}
+
+    def save_bins(self, bins) -> BinBlob:
+        """The state of the listed bins (int32 indices, device tensor or host sequence) as a BinBlob on the device: what
+        ``load_bins`` puts back, episode totals included.  Asynchronous on the current stream."""
+        bins = self._bins(bins)
+        info = self.bin_blob_info()
+        data = torch.zeros((bins.numel(), info["bytes_per_bin"]), dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.irbpp_save_bins(self._h, _ptr(bins), int(bins.numel()), _ptr(data), self._stream()), "irbpp_save_bins")
+        return BinBlob(info, data)
+
+    def load_bins(self, bins, blob: BinBlob) -> None:
+        """Bin ``bins[i]`` becomes what row i of ``blob`` was when it was saved (its totals too).  Raises for a blob of another
+        geometry, other shape / sequence tables or another layout version.  The observation the caller holds for these bins
+        is the caller's to restore (GpuVecEnv.save_state carries it)."""
+        bins = self._bins(bins)
+        if bins.numel() != blob.count:
+            raise ValueError("load_bins needs one bin per blob row")
+        info = _lib.IrbppBinBlobInfo(**blob.info)
+        data = blob.data.to(self.device).contiguous()
+        _lib.check(self.lib.irbpp_load_bins(self._h, C.byref(info), _ptr(bins), int(bins.numel()), _ptr(data), self._stream()),
+                   "irbpp_load_bins")
+        data.record_stream(torch.cuda.current_stream(self.device))
+
+    def _is_registered(self, obs: torch.Tensor) -> bool:
+        return any(t.data_ptr() == obs.data_ptr() for t in getattr(self, "_obs_buffers", []))
+
+    def fork_bins(self, src_bins, dst_bins, src_env: Optional["GpuPackingEnv"] = None, obs: Optional[torch.Tensor] = None,
+                  src_obs: Optional[torch.Tensor] = None, validate: bool = True) -> None:
+        """Bin ``dst_bins[i]`` of this environment continues from the state of bin ``src_bins[i]`` of ``src_env`` (default: this
+        one): same outputs call for call until the running episode ends, then its own next episode; its episode totals stay
+        (irbpp_copy_bins).  ``obs``: the caller's observation rows travel too, ``obs[dst] = (src_obs or obs)[src]``, on the
+        same stream; a registered buffer is invalidated, so the next step writes whole rows.  (The buffer of
+        ``set_auto_policy`` is the caller's as well and is not touched.)  ``validate`` (default, one
+        synchronisation): destinations pairwise distinct, no bin on both sides unless paired with itself, indices in range
+        -- ValueError otherwise; ``validate=False`` for hot loops: overlap is then the caller's contract, and an index out
+        of range skips its pair and raises BAD_BIN in ``check_device_error`` (the ``obs`` rows of such a pair are not
+        meaningful)."""
+        src_env = self if src_env is None else src_env
+        src, dst = src_env._bins(src_bins), self._bins(dst_bins)
+        if src.numel() != dst.numel():
+            raise ValueError("fork_bins needs as many source as destination bins")
+        if validate and src.numel():
+            # checks without data-dependent shapes, folded into one word: its read-back is the one synchronisation
+            s, d = src.long(), dst.long()
+            bad = (s.min() < 0) | (s.max() >= src_env.num_bins) | (d.min() < 0) | (d.max() >= self.num_bins)
+            ds = torch.sort(d).values
+            dup = (ds[1:] == ds[:-1]).any()
+            both = (torch.isin(d, s) & (s != d)).any() if src_env is self else torch.zeros_like(dup)
+            flags = int((bad.to(torch.int32) | (dup.to(torch.int32) << 1) | (both.to(torch.int32) << 2)).item())
+            if flags & 1:
+                raise ValueError("fork_bins: bin index outside the environment")
+            if flags & 2:
+                raise ValueError("fork_bins: destination bins must be pairwise distinct")
+            if flags & 4:
+                raise ValueError("fork_bins: a bin is both a source and a destination")
+        _lib.check(self.lib.irbpp_copy_bins(self._h, _ptr(dst), src_env._h, _ptr(src), int(dst.numel()), self._stream()),
+                   "irbpp_copy_bins")
+        if dst.numel() == 0 or obs is None:
+            return
+        s, d = src.long(), dst.long()
+        if not validate:             # (no index may fault a tensor copy: a pair the kernel skipped has raised BAD_BIN already)
+            s, d = s.clamp(0, src_env.num_bins - 1), d.clamp(0, self.num_bins - 1)
+        obs[d] = (obs if src_obs is None else src_obs)[s]
+        if self._is_registered(obs):
+            self.invalidate_obs_buffers(obs)
 
     def enable_placement_log(self, capacity: int = 256):
         """Device-side PackingGame.packed: (meta uint32-as-int32 [N,cap], z float64 [N,cap])."""
@@ -525,6 +646,102 @@ class GroupedPackingEnv(object):
                 out[torch.from_numpy(sel).to(self.device)] = self.groups[g].reset_bins(local)
         torch.cuda.synchronize(self.device)
         return out
+
+    # -- save, restore and fork bins: GpuPackingEnv's three methods with GLOBAL bin indices --------
+    @staticmethod
+    def _host_bins(bins) -> np.ndarray:
+        if isinstance(bins, torch.Tensor):
+            bins = bins.detach().cpu().numpy()
+        return np.asarray(bins, dtype=np.int64).reshape(-1)
+
+    def bin_blob_info(self) -> dict:
+        infos = [e.bin_blob_info() for e in self.groups]
+        return dict(infos[0], grids_current=int(all(i["grids_current"] for i in infos)))
+
+    def _group_of(self, idx: np.ndarray) -> np.ndarray:
+        """the group that answers for each global index (one out of range stays out of range in that group's local indices)"""
+        return np.clip(idx // self.per, 0, self.num_groups - 1)
+
+    def save_bins(self, bins) -> BinBlob:
+        """GpuPackingEnv.save_bins for global indices: one library call per group that owns a listed bin; rows in list
+        order.  Synchronises (a checkpoint is not a hot path)."""
+        idx = self._host_bins(bins)
+        self.synchronize()
+        info = self.bin_blob_info()
+        data = torch.zeros((len(idx), info["bytes_per_bin"]), dtype=torch.uint8, device=self.device)
+        grp = self._group_of(idx)
+        for g in range(self.num_groups):
+            sel = np.nonzero(grp == g)[0]
+            if len(sel):
+                data[torch.from_numpy(sel).to(self.device)] = self.groups[g].save_bins(idx[sel] - g * self.per).data
+        torch.cuda.synchronize(self.device)
+        return BinBlob(info, data)
+
+    def load_bins(self, bins, blob: BinBlob) -> None:
+        idx = self._host_bins(bins)
+        if len(idx) != blob.count:
+            raise ValueError("load_bins needs one bin per blob row")
+        self.synchronize()
+        data = blob.data.to(self.device)
+        grp = self._group_of(idx)
+        for g in range(self.num_groups):
+            sel = np.nonzero(grp == g)[0]
+            if len(sel):
+                part = data[torch.from_numpy(sel).to(self.device)].contiguous()
+                self.groups[g].load_bins(idx[sel] - g * self.per, BinBlob(blob.info, part))
+        torch.cuda.synchronize(self.device)
+
+    def fork_bins(self, src_bins, dst_bins, src_env=None, obs: Optional[torch.Tensor] = None,
+                  src_obs: Optional[torch.Tensor] = None, validate: bool = True) -> None:
+        """GpuPackingEnv.fork_bins for global indices; ``src_env``: this environment (default), another GroupedPackingEnv or a
+        GpuPackingEnv.  The pairs are split by (source group, destination group) -- on the host: index tensors on the
+        device cost a read-back -- and every non-empty pair of groups is one library call on the DESTINATION group's stream,
+        which waits for the caller's current stream and for the source group's stream first; the source group's stream then
+        waits for the copy, so its next step cannot overtake it.  ``obs`` ([num_bins, ...], rows by global index) travels on
+        the same streams.  ``validate`` checks the overlap contract on the host copies (no extra synchronisation)."""
+        src_env = self if src_env is None else src_env
+        s_idx, d_idx = self._host_bins(src_bins), self._host_bins(dst_bins)
+        if validate:
+            _check_fork_pairs(s_idx, d_idx, src_env.num_bins, self.num_bins, src_env is self)
+        elif len(s_idx) != len(d_idx):
+            raise ValueError("fork_bins needs as many source as destination bins")
+        cur = torch.cuda.current_stream(self.device)
+        if isinstance(src_env, GroupedPackingEnv):
+            s_parts = [(e, g * src_env.per, src_env.streams[g]) for g, e in enumerate(src_env.groups)]
+            s_grp = src_env._group_of(s_idx)
+        else:
+            s_parts, s_grp = [(src_env, 0, cur)], np.zeros(len(s_idx), dtype=np.int64)
+        d_grp = self._group_of(d_idx)
+        rows_from = obs if src_obs is None else src_obs
+        for gd in range(self.num_groups):
+            sd = self.streams[gd]
+            if not (d_grp == gd).any():
+                continue
+            if sd != cur:
+                sd.wait_stream(cur)
+                for t in (obs, rows_from):
+                    if t is not None:
+                        t.record_stream(sd)
+            for gs, (e_s, lo, ss) in enumerate(s_parts):
+                sel = np.nonzero((d_grp == gd) & (s_grp == gs))[0]
+                if not len(sel):
+                    continue
+                if ss != sd:
+                    sd.wait_stream(ss)
+                with torch.cuda.stream(sd):
+                    self.groups[gd].fork_bins((s_idx[sel] - lo).astype(np.int32), (d_idx[sel] - gd * self.per).astype(np.int32),
+                                              src_env=e_s, validate=False)
+                    if obs is not None:
+                        s_t = torch.from_numpy(np.clip(s_idx[sel], 0, src_env.num_bins - 1)).to(self.device)
+                        d_t = torch.from_numpy(np.clip(d_idx[sel], 0, self.num_bins - 1)).to(self.device)
+                        obs[d_t] = rows_from[s_t]
+                if ss != sd:
+                    ss.wait_stream(sd)
+            if obs is not None:                      # once per destination group, behind its pairs
+                block = obs[self.rows(gd)]
+                if self.groups[gd]._is_registered(block):
+                    with torch.cuda.stream(sd):
+                        self.groups[gd].invalidate_obs_buffers(block)
 
     def synchronize(self) -> None:
         for st in self.streams:
@@ -959,6 +1176,33 @@ class GpuVecEnv(object):
             e.invalidate_obs_buffers()
         self.env.check_device_error()
         return obs
+
+    def save_state(self, obs: Optional[torch.Tensor] = None) -> BinBlob:
+        """Every env's state as one BinBlob (``BinBlob.to_file`` writes it next to the model's checkpoint).  What ``infos``
+        and the other returns of ``step_wait`` are built from lives in the library and travels in the blob -- counters, the
+        episodes' sums, totals -- with ONE exception, the start time behind ``infos[i]['episode']['t']``: the blob carries
+        the seconds elapsed (``extra['elapsed_us']``) and ``load_state`` sets the clock back by them.  The wrapper keeps no
+        per-env bookkeeping of its own.  ``obs``: the observation the caller holds (what the next action is chosen from) is
+        stored along and handed back by ``load_state``; the library cannot rebuild it without stepping."""
+        if self.waiting_step or any(v is not None for v in self._group_pending.values()):
+            raise RuntimeError("save_state while a step is running")
+        blob = self.env.save_bins(np.arange(self.num_envs, dtype=np.int32))
+        blob.extra["elapsed_us"] = int((time.time() - self.tstart) * 1e6)
+        if obs is not None:
+            blob.extra["obs"] = obs.detach().clone()
+        return blob
+
+    def load_state(self, blob: BinBlob) -> Optional[torch.Tensor]:
+        """Every env becomes what ``save_state`` saved (after ``reset()`` on a new instance built from the same arguments:
+        other geometry or tables raise) -> the stored observation as a fresh device tensor, or None."""
+        if self.waiting_step or any(v is not None for v in self._group_pending.values()):
+            raise RuntimeError("load_state while a step is running")
+        if blob.count != self.num_envs:
+            raise ValueError("load_state needs a blob of all envs")
+        self.env.load_bins(np.arange(self.num_envs, dtype=np.int32), blob)
+        self.tstart = time.time() - int(blob.extra.get("elapsed_us", 0)) / 1e6
+        obs = blob.extra.get("obs")
+        return None if obs is None else obs.to(self.device).clone()
 
     def close(self):
         if not self.closed:
