@@ -597,6 +597,27 @@ int irbpp_dueling_target(const float* v_online_dev, int64_t v_online_stride, con
                          int64_t target_env_stride, int64_t target_row_stride, const float* returns_dev,
                          const float* nonterminals_dev, const float* support_dev, int32_t atoms, int32_t s_rows, int32_t batch,
                          float gamma_n, float v_min, float v_max, float delta_z, float* m_dev, int64_t* a_star_dev, void* stream);
+/* replaces: the part of Agent.learn that carries the gradient, forward: the end of DQNBPP.forward with log=True (model.py:395-398:
+ * v + a - a.mean(1), log_softmax over the atoms), log_ps[range(B), actions] and loss = -sum(m * log_ps_a, 1) (agent.py:85-86,
+ * 117) in one launch from the logits; the [batch][s_rows][atoms] log-probabilities never exist.  v_dev, a_dev strided as in
+ * irbpp_dueling_act; actions_dev int64[batch], an index in [-s_rows, 0) counting from the end; m_dev float32 [batch][atoms],
+ * contiguous (irbpp_dueling_target's m).  loss_out_dev float32[batch]; g_out_dev float32 [batch][atoms]: d loss / d x of the
+ * action's row, g = p * sum(m) - m, what irbpp_dueling_loss_backward starts from.  The float32 arithmetic is defined
+ * (csrc/irbpp_dueling_loss.hip: the column means and the exponential of irbpp_dueling_act, the library's own logarithm of the
+ * denominator, every sum in ascending atoms) and reproducible bit for bit.  An action outside [-s_rows, s_rows) accesses
+ * nothing out of range and gives loss = NaN, g = 0.  Finite logits and a finite non-negative m are the contract.
+ * IRBPP_ERR_ARG unless 2 <= atoms <= 128, 1 <= s_rows <= 1024, batch >= 1, v_stride >= atoms, row_stride >= atoms,
+ * env_stride >= (s_rows-1)*row_stride + atoms. */
+int irbpp_dueling_loss(const float* v_dev, int64_t v_stride, const float* a_dev, int64_t env_stride, int64_t row_stride,
+                       const int64_t* actions_dev, const float* m_dev, int32_t atoms, int32_t s_rows, int32_t batch,
+                       float* loss_out_dev, float* g_out_dev, void* stream);
+/* replaces: autograd's way back through the lines above, one launch: with gw = grad_loss[b] * g[b] and c = gw / (float)s_rows,
+ * grad_v_out_dev float32 [batch][atoms] = gw, and grad_a_out_dev float32 [batch][s_rows][atoms], dense and contiguous,
+ * = gw - c in the action's row and -c in every other row.  Either output may be NULL (that side needs no gradient); with both
+ * NULL nothing is launched.  g_dev, actions_dev as given to / written by irbpp_dueling_loss; grad_loss_dev float32[batch],
+ * contiguous.  Same limits on atoms, s_rows and batch. */
+int irbpp_dueling_loss_backward(const float* g_dev, const float* grad_loss_dev, const int64_t* actions_dev, int32_t atoms,
+                                int32_t s_rows, int32_t batch, float* grad_v_out_dev, float* grad_a_out_dev, void* stream);
 
 /* Tooling: when cycles_dev != NULL every later transition launch stores, per bin, one row
  * int64[num_bins][16]: shader-clock stamps 0 start, 1 action applied, 2 overlap test done,

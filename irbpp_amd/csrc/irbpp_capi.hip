@@ -24,6 +24,7 @@
 #include "irbpp_itemgen.hip"        // the item streams of irbpp_itemgen.h drawn on the device (irbpp_itemgen_dev_*, irbpp_stream_refill)
 #include "irbpp_c51.hip"            // the distributional head around the network (irbpp_categorical_act, irbpp_categorical_target)
 #include "irbpp_dueling.hip"        // the same from the network's logits: dueling combine + softmax fused in (irbpp_dueling_act, irbpp_dueling_target)
+#include "irbpp_dueling_loss.hip"   // the loss that carries the gradient, forward and backward from the logits (irbpp_dueling_loss, irbpp_dueling_loss_backward)
 #include "irbpp_metrics.hip"        // the trainer's episode metrics (irbpp_set_episode_window)
 #include "irbpp_itemgen.h"
 #include "irbpp_plan.h"             // which kernels a transition launches: the registry of kernels and plan_transition
@@ -1184,6 +1185,30 @@ int irbpp_dueling_target(const float* v_online_dev, int64_t v_online_stride, con
                        v_target_dev, (long long)v_target_stride, a_target_dev, (long long)target_env_stride,
                        (long long)target_row_stride, returns_dev, nonterminals_dev, support_dev, atoms, s_rows, gamma_n, v_min,
                        v_max, delta_z, m_dev, a_star_dev);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+int irbpp_dueling_loss(const float* v_dev, int64_t v_stride, const float* a_dev, int64_t env_stride, int64_t row_stride,
+                       const int64_t* actions_dev, const float* m_dev, int32_t atoms, int32_t s_rows, int32_t batch,
+                       float* loss_out_dev, float* g_out_dev, void* stream) {
+    if (!dueling_block_ok(v_dev, v_stride, a_dev, env_stride, row_stride, atoms, s_rows) || !actions_dev || !m_dev || batch < 1 ||
+        !loss_out_dev || !g_out_dev)
+        return IRBPP_ERR_ARG;
+    hipLaunchKernelGGL(irbpp_dueling_loss_kernel, dim3(batch), dim3(DUELING_THREADS), 0, (hipStream_t)stream, v_dev,
+                       (long long)v_stride, a_dev, (long long)env_stride, (long long)row_stride, actions_dev, m_dev, atoms, s_rows,
+                       loss_out_dev, g_out_dev);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+int irbpp_dueling_loss_backward(const float* g_dev, const float* grad_loss_dev, const int64_t* actions_dev, int32_t atoms,
+                                int32_t s_rows, int32_t batch, float* grad_v_out_dev, float* grad_a_out_dev, void* stream) {
+    if (!g_dev || !grad_loss_dev || !actions_dev || atoms < 2 || atoms > DUELING_MAX_ATOMS || s_rows < 1 ||
+        s_rows > DUELING_MAX_ROWS || batch < 1)
+        return IRBPP_ERR_ARG;
+    if (!grad_v_out_dev && !grad_a_out_dev) return IRBPP_OK;                   // nothing asked for: nothing launched
+    const int chunks = grad_a_out_dev ? (s_rows + DUELING_LOSS_CHUNK_ROWS - 1) / DUELING_LOSS_CHUNK_ROWS : 1;
+    hipLaunchKernelGGL(irbpp_dueling_loss_backward_kernel, dim3(batch, chunks), dim3(DUELING_THREADS), 0, (hipStream_t)stream,
+                       g_dev, grad_loss_dev, actions_dev, atoms, s_rows, grad_v_out_dev, grad_a_out_dev);
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
 }
 

@@ -574,6 +574,103 @@ def dueling_c51_target(v_online: torch.Tensor, a_online: torch.Tensor, v_target:
     return m, a_star
 
 
+# The same question for the loss below ("The dueling loss"): the kernels, since tools/dueling_loss_rates.py
+# measured forward + backward on an MI355X at 0.189 ms against 0.311 ms for the torch lines at a batch of 64 and 0.225 ms against
+# 0.425 ms at 512, with spreads of at most 0.031 ms (profiles/dueling_loss/).
+DUELING_LOSS_HIP_DEFAULT = True
+
+
+class _DuelingLossFunction(torch.autograd.Function):
+    """irbpp_dueling_loss / irbpp_dueling_loss_backward around autograd: v float32 [B, atoms] and a float32 [B, S, atoms] as
+    _dueling_v / _c51_block leave them, actions int64 [B] and m float32 [B, atoms] contiguous, all on one HIP device."""
+
+    @staticmethod
+    def forward(ctx, v, a, actions, m):
+        from . import _lib
+        lib = _lib.load()
+        B, S, atoms = a.shape
+        loss = torch.empty((B,), dtype=torch.float32, device=a.device)
+        g = torch.empty((B, atoms), dtype=torch.float32, device=a.device)
+        _lib.check(lib.irbpp_dueling_loss(_p(v), v.stride(0), _p(a), a.stride(0), a.stride(1), _p(actions), _p(m), atoms, S, B,
+                                          _p(loss), _p(g), _stream(a.device)), "irbpp_dueling_loss")
+        ctx.save_for_backward(g, actions)
+        ctx.rows = S
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        need_v, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_v or need_a):
+            return None, None, None, None
+        from . import _lib
+        lib = _lib.load()
+        g, actions = ctx.saved_tensors
+        B, atoms = g.shape
+        grad_loss = grad_loss.to(torch.float32).contiguous()      # loss.sum().backward() hands over a stride-0 expanded tensor
+        grad_v = torch.empty((B, atoms), dtype=torch.float32, device=g.device) if need_v else None
+        grad_a = torch.empty((B, ctx.rows, atoms), dtype=torch.float32, device=g.device) if need_a else None
+        _lib.check(lib.irbpp_dueling_loss_backward(_p(g), _p(grad_loss), _p(actions), atoms, ctx.rows, B, _p(grad_v), _p(grad_a),
+                                                   _stream(g.device)), "irbpp_dueling_loss_backward")
+        return grad_v, grad_a, None, None
+
+
+def dueling_c51_loss(v: torch.Tensor, a: torch.Tensor, actions: torch.Tensor, m: torch.Tensor, *,
+                     use_hip: Optional[bool] = None) -> torch.Tensor:
+    """The part of Agent.learn that carries the gradient, from the online network's logits of ``states`` (``v`` [B, atoms] or
+    [B, 1, atoms], ``a`` [B, S, atoms]): the end of DQNBPP.forward with log=True (model.py:395-398: ``v + a - a.mean(1)``,
+    log_softmax over the atoms), ``log_ps[range(B), actions]`` and ``-torch.sum(m * log_ps_a, 1)`` (agent.py:85-86, 117)
+    -> loss float32 [B], differentiable with respect to ``v`` and ``a``; ``m`` (dueling_c51_target's) is a constant.  With
+    ``use_hip=True`` (a HIP device; ``None`` takes DUELING_LOSS_HIP_DEFAULT) one kernel computes the loss in a defined float32
+    arithmetic (irbpp_dueling_loss: only the action's row and the column means, no [B, S, atoms] log-probabilities) and one
+    more writes the gradients (irbpp_dueling_loss_backward, only the sides that require one; ``v.grad`` in the shape ``v``
+    was given in); an action outside [-S, S) then gives a NaN loss and zero gradients.  Otherwise, and on the CPU, the
+    reference's torch lines run under ordinary autograd (and refuse such an action as torch indexing does)."""
+    v, a = _dueling_logits(v, a)
+    B, S, atoms = a.shape
+    if tuple(actions.shape) != (B,) or actions.dtype.is_floating_point:
+        raise ValueError(f"actions must be {B} integers")
+    if tuple(m.shape) != (B, atoms):
+        raise ValueError(f"m must be [{B}, {atoms}]")
+    m = m.detach()
+    lib = _hip_lib(a.device)
+    if use_hip and lib is None:
+        raise RuntimeError("use_hip=True needs a HIP device")
+    if lib is None or not (DUELING_LOSS_HIP_DEFAULT if use_hip is None else use_hip):
+        q = v.unsqueeze(1) + a - a.mean(1, keepdim=True)
+        log_ps = torch.log_softmax(q, dim=2)
+        log_ps_a = log_ps[torch.arange(B, device=a.device), actions.to(device=a.device, dtype=torch.int64)]
+        return -torch.sum(m.to(a.device) * log_ps_a, 1)
+    dev = a.device
+    return _DuelingLossFunction.apply(_dueling_v(v), _c51_block(a), actions.to(device=dev, dtype=torch.int64).contiguous(),
+                                      m.to(device=dev, dtype=torch.float32).contiguous())
+
+
+def learn_loss(online_logits, target_logits, batch, support: torch.Tensor, gamma_n: float, v_min: float, v_max: float, *,
+               use_hip: Optional[bool] = None) -> torch.Tensor:
+    """Agent.learn from the sampled batch to the per-sample loss (agent.py:84-117) as three network calls and two head calls.
+    ``online_logits`` / ``target_logits`` are callables ``states -> (v, a)``: the networks up to their logits (DQNBPP.forward
+    before model.py:395); ``batch`` is what VectorReplayMemory.sample returns.  -> loss float32 [B], attached to the online
+    network's graph.  What stays the caller's (agent.py:118-124)::
+
+        tree_idxs, *_, weights = batch
+        loss = learn_loss(online_net.logits, target_net.logits, batch, support, discount ** n, Vmin, Vmax)
+        online_net.zero_grad()
+        (weights * loss).mean().backward()
+        clip_grad_norm_(online_net.parameters(), norm_clip)
+        optimiser.step()
+        memory.update_priorities(tree_idxs, loss.detach())
+
+    ``use_hip`` is handed to both head calls (``None``: each one's own default)."""
+    _, states, actions, returns, next_states, nonterminals, _ = batch
+    v, a = online_logits(states)
+    with torch.no_grad():
+        v_on, a_on = online_logits(next_states)
+        v_tg, a_tg = target_logits(next_states)
+        m, _ = dueling_c51_target(v_on, a_on, v_tg, a_tg, returns, nonterminals, support, gamma_n, v_min, v_max, use_hip=use_hip)
+    return dueling_c51_loss(v, a, actions, m, use_hip=use_hip)
+
+
 def actor_step(envs, policy, memory: VectorReplayMemory, state: torch.Tensor, reward_clip: float = 0.0):
     """One iteration of the trainer's acting loop (trainer.py:160-186) without per-env Python:
     mask -> policy -> envs.step -> clip -> append.  ``envs`` is a GpuPackingEnv (device-tensor
