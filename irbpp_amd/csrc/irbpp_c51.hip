@@ -7,26 +7,22 @@
 // -ffp-contract=off), z the caller's own torch.linspace support.  Only the loading is free: a wave stages 64 rows at a
 // time through LDS with coalesced dword loads (consecutive lanes, consecutive addresses of the row-major block) and
 // then sums lane-per-row from LDS; rows lie `atoms | 1` floats apart there, an odd pitch, so the 32 lanes of a
-// ds_read_b32 group fall on 32 different banks.  p is read exactly once.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
+// ds_read_b32 group fall on 32 different banks.  p is read exactly once.  The arg-max rule and the categorical projection
+// are those of irbpp_head.h.
+#include "irbpp_head.h"
 
 namespace irbpp {
 
-constexpr int C51_MAX_ATOMS = 128;
-constexpr int C51_MAX_ROWS = 1024;
-
 // One wave (a 64-thread workgroup): arg-max over the s_rows rows of one [S][atoms] block of the defined expected value;
-// the first maximum wins, and with every row at -inf index 0 does (the rules of irbpp_masked_argmax_kernel).  flags
-// (may be NULL) is the env's observation row: row i counts as -inf when flags[5*i+4] == 0.  q_out (may be NULL) receives
-// the unmasked values.  tile: 64 * (atoms | 1) floats of LDS.  Every lane returns the index.
+// the first maximum wins, and with every row at -inf index 0 does (head_better, head_index).  flags (may be NULL) is the
+// env's observation row (head_masked).  q_out (may be NULL) receives the unmasked values.  tile: 64 * (atoms | 1) floats
+// of LDS.  Every lane returns the index.
 __device__ __forceinline__ int c51_wave_argmax(const float* __restrict__ p, long long row_stride, const float* __restrict__ z,
                                                int atoms, int s_rows, const float* __restrict__ flags,
                                                float* __restrict__ q_out, float* tile) {
     const int lane = threadIdx.x;
     const int pitch = atoms | 1;
-    // element k = lane + 64 t of the 64-row chunk is (row, a) = (k / atoms, k % atoms): stepped, not divided
+    // head_walk<64>'s steps, kept in the form these two kernels were measured in: fixed trip count, unrolled, the guard inside
     const int q64 = 64 / atoms, r64 = 64 - q64 * atoms;
     const int row0 = lane / atoms, a0 = lane - row0 * atoms;
     float best = -INFINITY;
@@ -49,17 +45,13 @@ __device__ __forceinline__ int c51_wave_argmax(const float* __restrict__ p, long
             float s = rw[0] * z[0];
             for (int k = 1; k < atoms; ++k) s = s + rw[k] * z[k];
             if (q_out) q_out[i] = s;
-            const float v = (flags && flags[i * 5 + 4] == 0.0f) ? -INFINITY : s;
-            if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+            const float v = head_masked(flags, i, s);
+            if (head_better(v, i, best, bi)) { best = v; bi = i; }
         }
         __syncthreads();                                 // the tile is rewritten by the next trip
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o);
-        const int oi = __shfl_xor(bi, o);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    return bi < s_rows ? bi : 0;                         // (NaN values, out of scope, match nothing: still a row of the block)
+    head_wave_argmax(best, bi);
+    return head_index(bi, s_rows);
 }
 
 // Agent.act (agent.py:51-58) after the network: (q_map * support).sum(2), sum_q_map[(1 - mask).bool()] = -inf, argmax(1),
@@ -78,12 +70,7 @@ irbpp_c51_act_kernel(const float* __restrict__ p, long long env_stride, long lon
 }
 
 // Agent.learn (agent.py:88-115) after the two network calls, one wave per sample: a* = argmax of the (unmasked, :92)
-// expected value of p_online, pns_a = p_target[b][a*], Tz = R + (nonterminal * gamma^n) z clamped to [Vmin, Vmax],
-// b = (Tz - Vmin) / delta_z (IEEE division), l = floor b, u = ceil b with the two l == u fix-ups in the reference's order
-// (:108-109), and the two index_add_ calls (:114-115) without atomics: l, u and the two weights of every atom go to LDS and
-// lane j sums, in ascending i, first the l == j contributions pns_a[i] (u_i - b_i) and then the u == j contributions
-// pns_a[i] (b_i - l_i) -- the order in which the reference's two sequential scatters reach m[j].  An l or u outside
-// [0, atoms) (a delta_z that is not (Vmax - Vmin) / (atoms - 1)) matches no lane: nothing is written out of range.
+// expected value of p_online, pns_a = p_target[b][a*], and head_project's projection of it onto the support.
 extern "C" __global__ void __launch_bounds__(64)
 irbpp_c51_target_kernel(const float* __restrict__ p_online, long long on_env_stride, long long on_row_stride,
                         const float* __restrict__ p_target, long long tg_env_stride, long long tg_row_stride,
@@ -91,37 +78,14 @@ irbpp_c51_target_kernel(const float* __restrict__ p_online, long long on_env_str
                         const float* __restrict__ support, int atoms, int s_rows, float gamma_n, float v_min, float v_max,
                         float delta_z, float* __restrict__ m, int64_t* __restrict__ a_star) {
     HIP_DYNAMIC_SHARED(float, c51_tile)                 // 64 * (atoms | 1) floats
-    __shared__ int sl[C51_MAX_ATOMS], su[C51_MAX_ATOMS];
-    __shared__ float swl[C51_MAX_ATOMS], swu[C51_MAX_ATOMS];
+    __shared__ HeadProjection proj;
     const int smp = blockIdx.x, lane = threadIdx.x;
     const int best = c51_wave_argmax(p_online + (size_t)smp * on_env_stride, on_row_stride, support, atoms, s_rows, nullptr,
                                      nullptr, c51_tile);
     if (lane == 0) a_star[smp] = best;
     const float* pa = p_target + (size_t)smp * tg_env_stride + (size_t)best * tg_row_stride;
-    const float ret = returns[smp];
-    const float g = nonterminals[smp] * gamma_n;
-    for (int i = lane; i < atoms; i += 64) {
-        float tz = ret + g * support[i];
-        tz = fminf(fmaxf(tz, v_min), v_max);
-        const float b = (tz - v_min) / delta_z;
-        int l = (int)floorf(b), u = (int)ceilf(b);
-        if (u > 0 && l == u) l -= 1;                     // l[(u > 0) * (l == u)] -= 1
-        if (l < atoms - 1 && l == u) u += 1;             // u[(l < (atoms - 1)) * (l == u)] += 1
-        const float pi = pa[i];
-        sl[i] = l;
-        su[i] = u;
-        swl[i] = pi * ((float)u - b);
-        swu[i] = pi * (b - (float)l);
-    }
-    __syncthreads();
-    for (int j = lane; j < atoms; j += 64) {
-        float acc = 0.0f;
-        for (int i = 0; i < atoms; ++i)
-            if (sl[i] == j) acc = acc + swl[i];
-        for (int i = 0; i < atoms; ++i)
-            if (su[i] == j) acc = acc + swu[i];
-        m[(size_t)smp * atoms + j] = acc;
-    }
+    head_project<64>(pa, support, returns[smp], nonterminals[smp] * gamma_n, v_min, v_max, delta_z, atoms, m + (size_t)smp * atoms,
+                     proj);
 }
 
 }  // namespace irbpp

@@ -1109,15 +1109,16 @@ int irbpp_masked_argmax(const float* q_dev, int32_t q_stride, const float* obs_d
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
 }
 
-static bool c51_block_ok(const float* p, int64_t env_stride, int64_t row_stride, int32_t atoms, int32_t s_rows) {
-    return p && atoms >= 2 && atoms <= C51_MAX_ATOMS && s_rows >= 1 && s_rows <= C51_MAX_ROWS && row_stride >= atoms &&
+// one [S][atoms] block per env / sample: within the head's limits, rows and envs that do not overlap
+static bool head_block_ok(const float* p, int64_t env_stride, int64_t row_stride, int32_t atoms, int32_t s_rows) {
+    return p && atoms >= 2 && atoms <= HEAD_MAX_ATOMS && s_rows >= 1 && s_rows <= HEAD_MAX_ROWS && row_stride >= atoms &&
            env_stride >= (int64_t)(s_rows - 1) * row_stride + atoms;
 }
 
 int irbpp_categorical_act(const float* p_dev, int64_t env_stride, int64_t row_stride, const float* support_dev, int32_t atoms,
                           const float* obs_dev, int32_t obs_stride, int32_t s_rows, int32_t n_env, int64_t* action_dev,
                           float* q_out_dev, int64_t q_stride, void* stream) {
-    if (!c51_block_ok(p_dev, env_stride, row_stride, atoms, s_rows) || !support_dev || !action_dev || n_env < 1 ||
+    if (!head_block_ok(p_dev, env_stride, row_stride, atoms, s_rows) || !support_dev || !action_dev || n_env < 1 ||
         (obs_dev && obs_stride < 5 * s_rows) || (q_out_dev && q_stride < s_rows))
         return IRBPP_ERR_ARG;
     hipLaunchKernelGGL(irbpp_c51_act_kernel, dim3(n_env), dim3(64), (size_t)64 * (atoms | 1) * sizeof(float), (hipStream_t)stream,
@@ -1130,8 +1131,8 @@ int irbpp_categorical_target(const float* p_online_dev, int64_t online_env_strid
                              const float* p_target_dev, int64_t target_env_stride, int64_t target_row_stride, const float* returns_dev,
                              const float* nonterminals_dev, const float* support_dev, int32_t atoms, int32_t s_rows, int32_t batch,
                              float gamma_n, float v_min, float v_max, float delta_z, float* m_dev, int64_t* a_star_dev, void* stream) {
-    if (!c51_block_ok(p_online_dev, online_env_stride, online_row_stride, atoms, s_rows) ||
-        !c51_block_ok(p_target_dev, target_env_stride, target_row_stride, atoms, s_rows) || !returns_dev || !nonterminals_dev ||
+    if (!head_block_ok(p_online_dev, online_env_stride, online_row_stride, atoms, s_rows) ||
+        !head_block_ok(p_target_dev, target_env_stride, target_row_stride, atoms, s_rows) || !returns_dev || !nonterminals_dev ||
         !support_dev || !m_dev || !a_star_dev || batch < 1 || !(v_max > v_min) || !(delta_z > 0))
         return IRBPP_ERR_ARG;
     hipLaunchKernelGGL(irbpp_c51_target_kernel, dim3(batch), dim3(64), (size_t)64 * (atoms | 1) * sizeof(float),
@@ -1143,8 +1144,7 @@ int irbpp_categorical_target(const float* p_online_dev, int64_t online_env_strid
 
 static bool dueling_block_ok(const float* v, int64_t v_stride, const float* a, int64_t env_stride, int64_t row_stride, int32_t atoms,
                              int32_t s_rows) {
-    return v && a && atoms >= 2 && atoms <= DUELING_MAX_ATOMS && s_rows >= 1 && s_rows <= DUELING_MAX_ROWS && v_stride >= atoms &&
-           row_stride >= atoms && env_stride >= (int64_t)(s_rows - 1) * row_stride + atoms;
+    return v && v_stride >= atoms && head_block_ok(a, env_stride, row_stride, atoms, s_rows);
 }
 
 // dynamic LDS of a dueling launch; above 64 KB the kernel is told (on the current device) that it may be given that much
@@ -1202,8 +1202,8 @@ int irbpp_dueling_loss(const float* v_dev, int64_t v_stride, const float* a_dev,
 
 int irbpp_dueling_loss_backward(const float* g_dev, const float* grad_loss_dev, const int64_t* actions_dev, int32_t atoms,
                                 int32_t s_rows, int32_t batch, float* grad_v_out_dev, float* grad_a_out_dev, void* stream) {
-    if (!g_dev || !grad_loss_dev || !actions_dev || atoms < 2 || atoms > DUELING_MAX_ATOMS || s_rows < 1 ||
-        s_rows > DUELING_MAX_ROWS || batch < 1)
+    if (!g_dev || !grad_loss_dev || !actions_dev || atoms < 2 || atoms > HEAD_MAX_ATOMS || s_rows < 1 ||
+        s_rows > HEAD_MAX_ROWS || batch < 1)
         return IRBPP_ERR_ARG;
     if (!grad_v_out_dev && !grad_a_out_dev) return IRBPP_OK;                   // nothing asked for: nothing launched
     const int chunks = grad_a_out_dev ? (s_rows + DUELING_LOSS_CHUNK_ROWS - 1) / DUELING_LOSS_CHUNK_ROWS : 1;

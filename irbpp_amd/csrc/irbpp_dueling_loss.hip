@@ -2,12 +2,12 @@
 // DQNBPP.forward with log=True (model.py:395-398: q = v + a - a.mean(1), log_softmax over the atoms), log_ps[range(B), actions]
 // and loss = -sum(m * log_ps_a, 1) (agent.py:85-86, 117) in one launch, and autograd's way back through all of that in a
 // second one.  Only row actions[b] of a sample's block enters the loss; the block is read for its column means alone.
-// Included after irbpp_dueling.hip (DuelingShared, dueling_mean, dueling_dexp and the limits are used from there).
+// DuelingShared, dueling_mean, dueling_combine, dueling_dexp and the limits are those of irbpp_head.h.
 //
 // Defined float32 arithmetic (multiply and add separate, -ffp-contract=off; tests/test_dueling_loss_cpu.py restates it in
 // numpy and the kernels are held to it bit for bit).  For one sample: v[atoms], a[S][atoms], the action row r, the target
 // distribution m[atoms], the upstream gradient w:
-//   mean[k] = dueling_mean of irbpp_dueling.hip (16 interleaved partial sums, added left to right, / (float)S)
+//   mean[k] = dueling_mean of irbpp_head.h (16 interleaved partial sums, added left to right, / (float)S)
 //   x[k]    = (v[k] + a[r][k]) - mean[k];   mx = max_k x[k];   t[k] = x[k] - mx;   e[k] = dueling_dexp(t[k])
 //   den     = ((e[0] + e[1]) + ..) + e[atoms-1]                         in [1, atoms]: the maximum's e is dexp(0) = 1
 //   L       = dlog(den);   lp[k] = t[k] - L
@@ -21,10 +21,7 @@
 // An action in [-S, 0) counts from the end, as torch indexing does.  One outside [-S, S) reads and writes nothing out of
 // range: loss = NaN, g = 0 (so every gradient of that sample is zero).  Finite logits and a finite non-negative m are the
 // contract.  The values are a function of (S, atoms) and the inputs alone: not of the batch, the strides or the grid.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-#include <string.h>
+#include "irbpp_head.h"
 
 namespace irbpp {
 
@@ -63,13 +60,7 @@ __device__ __forceinline__ float dueling_dlog(float d) {
 // The action's row, sequential in k by definition.  rw: a[r] on entry, g on return; se: scratch for e; sv, smean, sm: LDS
 // copies of v, mean and m.  Returns the loss.
 __device__ __forceinline__ float dueling_loss_row(float* rw, float* se, const float* sv, const float* smean, const float* sm, int atoms) {
-    float mx = (sv[0] + rw[0]) - smean[0];
-    rw[0] = mx;
-    for (int k = 1; k < atoms; ++k) {
-        const float x = (sv[k] + rw[k]) - smean[k];
-        rw[k] = x;
-        mx = x > mx ? x : mx;
-    }
+    const float mx = dueling_combine(rw, sv, smean, atoms);
     float den = 0.0f;
     for (int k = 0; k < atoms; ++k) {
         const float t = rw[k] - mx;
@@ -95,7 +86,7 @@ irbpp_dueling_loss_kernel(const float* __restrict__ v, long long v_stride, const
                           long long row_stride, const int64_t* __restrict__ actions, const float* __restrict__ m, int atoms,
                           int s_rows, float* __restrict__ loss, float* __restrict__ g) {
     __shared__ DuelingShared sh;                         // sh.z holds m
-    __shared__ float srow[DUELING_MAX_ATOMS], se[DUELING_MAX_ATOMS];
+    __shared__ float srow[HEAD_MAX_ATOMS], se[HEAD_MAX_ATOMS];
     const int smp = blockIdx.x, tid = threadIdx.x;
     long long r = actions[smp];
     if (r < 0) r += s_rows;
@@ -120,13 +111,13 @@ irbpp_dueling_loss_kernel(const float* __restrict__ v, long long v_stride, const
 }
 
 // Workgroup (smp, chunk): gw and c of the sample once into LDS as the two values a grad_a element can take, then rows
-// chunk * 64 .. of the dense grad_a[smp] with coalesced dword stores, element e = tid + 512 t of the chunk being (row, k) =
-// (e / atoms, e % atoms): stepped, not divided.  Chunk 0 writes grad_v.  Either output may be NULL.
+// chunk * 64 .. of the dense grad_a[smp] with coalesced dword stores (head_walk).  Chunk 0 writes grad_v.  Either output may
+// be NULL.
 extern "C" __global__ void __launch_bounds__(DUELING_THREADS)
 irbpp_dueling_loss_backward_kernel(const float* __restrict__ g, const float* __restrict__ grad_loss,
                                    const int64_t* __restrict__ actions, int atoms, int s_rows, float* __restrict__ grad_v,
                                    float* __restrict__ grad_a) {
-    __shared__ float hit[DUELING_MAX_ATOMS], miss[DUELING_MAX_ATOMS];
+    __shared__ float hit[HEAD_MAX_ATOMS], miss[HEAD_MAX_ATOMS];
     const int smp = blockIdx.x, r0 = blockIdx.y * DUELING_LOSS_CHUNK_ROWS, tid = threadIdx.x;
     if (tid < atoms) {
         const float gw = grad_loss[smp] * g[(size_t)smp * atoms + tid];
@@ -142,15 +133,7 @@ irbpp_dueling_loss_backward_kernel(const float* __restrict__ g, const float* __r
     const int hit_row = (r >= r0 && r < r0 + DUELING_LOSS_CHUNK_ROWS) ? (int)(r - r0) : -1;
     const int nrows = s_rows - r0 < DUELING_LOSS_CHUNK_ROWS ? s_rows - r0 : DUELING_LOSS_CHUNK_ROWS;
     float* dst = grad_a + ((size_t)smp * s_rows + r0) * atoms;
-    const int q = DUELING_THREADS / atoms, rem = DUELING_THREADS - q * atoms;
-    int row = tid / atoms, k = tid - row * atoms, e = tid;
-    while (row < nrows) {
-        dst[e] = row == hit_row ? hit[k] : miss[k];
-        e += DUELING_THREADS;
-        row += q;
-        k += rem;
-        if (k >= atoms) { k -= atoms; ++row; }
-    }
+    head_walk<DUELING_THREADS>(atoms, nrows, [&](int row, int k, int e) { dst[e] = row == hit_row ? hit[k] : miss[k]; });
 }
 
 }  // namespace irbpp

@@ -364,11 +364,35 @@ def masked_greedy_action(q: torch.Tensor, state: torch.Tensor, selected_action: 
 C51_HIP_DEFAULT = False
 
 
-def _c51_lib(t: torch.Tensor, use_hip: Optional[bool]):
+def _head_lib(t: torch.Tensor, use_hip: Optional[bool], default: bool):
+    """The library if a head wrapper is to take its kernels on t's device, else None; ``default``: its *_HIP_DEFAULT."""
     lib = _hip_lib(t.device)
     if use_hip and lib is None:
         raise RuntimeError("use_hip=True needs a HIP device")
-    return lib if (C51_HIP_DEFAULT if use_hip is None else use_hip) else None
+    return lib if (default if use_hip is None else use_hip) else None
+
+
+def _f32(x: torch.Tensor, device) -> torch.Tensor:
+    return x.to(device=device, dtype=torch.float32).contiguous()
+
+
+def _obs_arg(state: Optional[torch.Tensor]):
+    """(state as float32 with contiguous rows, its env stride); (None, 0) without a mask."""
+    if state is None:
+        return None, 0
+    state = state.to(torch.float32)
+    if state.stride(1) != 1:
+        state = state.contiguous()
+    return state, state.stride(0)
+
+
+def _q_out_arg(q_out: Optional[torch.Tensor], N: int, S: int, device, name: str) -> int:
+    """q_out's row stride (0 without one); ``name``: the caller's word for the tensor whose device q_out must share."""
+    if q_out is None:
+        return 0
+    if q_out.dtype != torch.float32 or q_out.device != device or tuple(q_out.shape) != (N, S) or q_out.stride(1) != 1:
+        raise ValueError(f"q_out must be a float32 [N, S] tensor on {name}'s device with contiguous rows")
+    return q_out.stride(0)
 
 
 def _c51_block(p: torch.Tensor) -> torch.Tensor:
@@ -392,7 +416,7 @@ def distributional_greedy_action(p: torch.Tensor, support: torch.Tensor, state: 
     N, S, atoms = p.shape
     if selected_action is not None and int(selected_action) != S:
         raise ValueError(f"selected_action {selected_action} != {S} candidate rows")
-    lib = _c51_lib(p, use_hip)
+    lib = _head_lib(p, use_hip, C51_HIP_DEFAULT)
     if lib is None:
         q = (p * support).sum(2)
         if q_out is not None:
@@ -402,18 +426,9 @@ def distributional_greedy_action(p: torch.Tensor, support: torch.Tensor, state: 
         return q.argmax(1)
     from . import _lib
     p = _c51_block(p)
-    support = support.to(device=p.device, dtype=torch.float32).contiguous()
-    obs_stride = 0
-    if state is not None:
-        state = state.to(torch.float32)
-        if state.stride(1) != 1:
-            state = state.contiguous()
-        obs_stride = state.stride(0)
-    q_stride = 0
-    if q_out is not None:
-        if q_out.dtype != torch.float32 or q_out.device != p.device or tuple(q_out.shape) != (N, S) or q_out.stride(1) != 1:
-            raise ValueError("q_out must be a float32 [N, S] tensor on p's device with contiguous rows")
-        q_stride = q_out.stride(0)
+    support = _f32(support, p.device)
+    state, obs_stride = _obs_arg(state)
+    q_stride = _q_out_arg(q_out, N, S, p.device, "p")
     out = torch.empty((N,), dtype=torch.int64, device=p.device)
     _lib.check(lib.irbpp_categorical_act(_p(p), p.stride(0), p.stride(1), _p(support), atoms, _p(state), obs_stride, S, N, _p(out),
                                          _p(q_out), q_stride, _stream(p.device)), "irbpp_categorical_act")
@@ -434,7 +449,7 @@ def c51_target(p_online: torch.Tensor, p_target: torch.Tensor, returns: torch.Te
         raise ValueError("p_online and p_target must have the same [B, S, atoms] shape")
     delta_z = (v_max - v_min) / (atoms - 1)
     returns, nonterminals = returns.reshape(B), nonterminals.reshape(B)
-    lib = _c51_lib(p_online, use_hip)
+    lib = _head_lib(p_online, use_hip, C51_HIP_DEFAULT)
     if lib is None:
         a_star = (support.expand_as(p_online) * p_online).sum(2).argmax(1)
         pns_a = p_target[torch.arange(B, device=p_target.device), a_star]
@@ -452,8 +467,7 @@ def c51_target(p_online: torch.Tensor, p_target: torch.Tensor, returns: torch.Te
     from . import _lib
     dev = p_online.device
     p_online, p_target = _c51_block(p_online), _c51_block(p_target)
-    f32 = lambda x: x.to(device=dev, dtype=torch.float32).contiguous()      # noqa: E731
-    returns, nonterminals, support = f32(returns), f32(nonterminals), f32(support)
+    returns, nonterminals, support = _f32(returns, dev), _f32(nonterminals, dev), _f32(support, dev)
     m = torch.empty((B, atoms), dtype=torch.float32, device=dev)
     a_star = torch.empty((B,), dtype=torch.int64, device=dev)
     _lib.check(lib.irbpp_categorical_target(_p(p_online), p_online.stride(0), p_online.stride(1), _p(p_target), p_target.stride(0),
@@ -467,13 +481,6 @@ def c51_target(p_online: torch.Tensor, p_target: torch.Tensor, returns: torch.Te
 # head"): the kernels, since tools/dueling_head_rates.py measured them on an MI355X at 0.22 ms against 0.63 ms for the torch
 # lines (4096 envs) and 0.031 ms against 0.48 ms (a learn batch of 64), far outside the spread (profiles/dueling_head/).
 DUELING_HIP_DEFAULT = True
-
-
-def _dueling_lib(t: torch.Tensor, use_hip: Optional[bool]):
-    lib = _hip_lib(t.device)
-    if use_hip and lib is None:
-        raise RuntimeError("use_hip=True needs a HIP device")
-    return lib if (DUELING_HIP_DEFAULT if use_hip is None else use_hip) else None
 
 
 def _dueling_logits(v: torch.Tensor, a: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -513,7 +520,7 @@ def dueling_greedy_action(v: torch.Tensor, a: torch.Tensor, support: torch.Tenso
     N, S, atoms = a.shape
     if selected_action is not None and int(selected_action) != S:
         raise ValueError(f"selected_action {selected_action} != {S} candidate rows")
-    lib = _dueling_lib(a, use_hip)
+    lib = _head_lib(a, use_hip, DUELING_HIP_DEFAULT)
     if lib is None:
         p = _dueling_softmax(v, a)
         if p_out is not None:
@@ -521,18 +528,9 @@ def dueling_greedy_action(v: torch.Tensor, a: torch.Tensor, support: torch.Tenso
         return distributional_greedy_action(p, support, state, selected_action, q_out, use_hip=False)
     from . import _lib
     v, a = _dueling_v(v), _c51_block(a)
-    support = support.to(device=a.device, dtype=torch.float32).contiguous()
-    obs_stride = 0
-    if state is not None:
-        state = state.to(torch.float32)
-        if state.stride(1) != 1:
-            state = state.contiguous()
-        obs_stride = state.stride(0)
-    q_stride = 0
-    if q_out is not None:
-        if q_out.dtype != torch.float32 or q_out.device != a.device or tuple(q_out.shape) != (N, S) or q_out.stride(1) != 1:
-            raise ValueError("q_out must be a float32 [N, S] tensor on a's device with contiguous rows")
-        q_stride = q_out.stride(0)
+    support = _f32(support, a.device)
+    state, obs_stride = _obs_arg(state)
+    q_stride = _q_out_arg(q_out, N, S, a.device, "a")
     if p_out is not None and (p_out.dtype != torch.float32 or p_out.device != a.device or tuple(p_out.shape) != (N, S, atoms) or
                               not p_out.is_contiguous()):
         raise ValueError("p_out must be a contiguous float32 [N, S, atoms] tensor on a's device")
@@ -555,7 +553,7 @@ def dueling_c51_target(v_online: torch.Tensor, a_online: torch.Tensor, v_target:
     B, S, atoms = a_online.shape
     if tuple(a_target.shape) != (B, S, atoms):
         raise ValueError("a_online and a_target must have the same [B, S, atoms] shape")
-    lib = _dueling_lib(a_online, use_hip)
+    lib = _head_lib(a_online, use_hip, DUELING_HIP_DEFAULT)
     if lib is None:
         return c51_target(_dueling_softmax(v_online, a_online), _dueling_softmax(v_target, a_target), returns, nonterminals,
                           support, gamma_n, v_min, v_max, use_hip=False)
@@ -563,8 +561,7 @@ def dueling_c51_target(v_online: torch.Tensor, a_online: torch.Tensor, v_target:
     dev = a_online.device
     delta_z = (v_max - v_min) / (atoms - 1)
     v_online, v_target, a_online, a_target = _dueling_v(v_online), _dueling_v(v_target), _c51_block(a_online), _c51_block(a_target)
-    f32 = lambda x: x.to(device=dev, dtype=torch.float32).contiguous()      # noqa: E731
-    returns, nonterminals, support = f32(returns.reshape(B)), f32(nonterminals.reshape(B)), f32(support)
+    returns, nonterminals, support = _f32(returns.reshape(B), dev), _f32(nonterminals.reshape(B), dev), _f32(support, dev)
     m = torch.empty((B, atoms), dtype=torch.float32, device=dev)
     a_star = torch.empty((B,), dtype=torch.int64, device=dev)
     _lib.check(lib.irbpp_dueling_target(_p(v_online), v_online.stride(0), _p(a_online), a_online.stride(0), a_online.stride(1),
@@ -633,17 +630,14 @@ def dueling_c51_loss(v: torch.Tensor, a: torch.Tensor, actions: torch.Tensor, m:
     if tuple(m.shape) != (B, atoms):
         raise ValueError(f"m must be [{B}, {atoms}]")
     m = m.detach()
-    lib = _hip_lib(a.device)
-    if use_hip and lib is None:
-        raise RuntimeError("use_hip=True needs a HIP device")
-    if lib is None or not (DUELING_LOSS_HIP_DEFAULT if use_hip is None else use_hip):
+    if _head_lib(a, use_hip, DUELING_LOSS_HIP_DEFAULT) is None:
         q = v.unsqueeze(1) + a - a.mean(1, keepdim=True)
         log_ps = torch.log_softmax(q, dim=2)
         log_ps_a = log_ps[torch.arange(B, device=a.device), actions.to(device=a.device, dtype=torch.int64)]
         return -torch.sum(m.to(a.device) * log_ps_a, 1)
     dev = a.device
     return _DuelingLossFunction.apply(_dueling_v(v), _c51_block(a), actions.to(device=dev, dtype=torch.int64).contiguous(),
-                                      m.to(device=dev, dtype=torch.float32).contiguous())
+                                      _f32(m, dev))
 
 
 def learn_loss(online_logits, target_logits, batch, support: torch.Tensor, gamma_n: float, v_min: float, v_max: float, *,

@@ -1,70 +1,15 @@
 // Host harness (test infrastructure): the two kernels of irbpp_amd/csrc/irbpp_dueling_loss.hip run on the CPU, one workgroup at
-// a time, by 512 threads in lockstep (the workgroup's size), in the manner of dueling_host.cpp: __syncthreads is a real
-// barrier, static __shared__ objects are statics, blockIdx has the two dimensions the backward kernel's grid has.  The
-// kernels' own source is compiled (with irbpp_dueling.hip in front of it, as in the library), so their indexing, the column
+// a time, by 512 threads in lockstep (the workgroup's size; lockstep.h: barriers, __shared__, and a blockIdx of the two
+// dimensions the backward kernel's grid has).  The kernels' own source is compiled, so their indexing, the column
 // means, the row loop and the stepped stores are what the CPU suite checks against the numpy definition; float arithmetic is
 // IEEE float32 on both sides (build with -ffp-contract=off).
 // With -DDUELING_LOSS_HOST_MAIN the file is a program of its own (for a sanitizer build): it runs both kernels over a few
 // shapes in buffers of exactly the size they may touch and prints a checksum.
-#include <math.h>
-#include <pthread.h>
-#include <stdint.h>
 #include <stdio.h>
 
-#include <thread>
-#include <vector>
+#include "lockstep.h"
 
-#define __device__
-#define __host__
-#define __global__
-#define __forceinline__ inline
-#define __shared__ static
-#define __launch_bounds__(n)
-#define HIP_DYNAMIC_SHARED(type, var) type* var = (type*)g_tile;
-
-constexpr int HOST_THREADS = 512;
-static thread_local struct { unsigned x; } threadIdx;
-static struct { unsigned x, y; } blockIdx;
-static pthread_barrier_t g_bar;
-static float g_tile[144 * 1024 / 4];                     // (the kernels of irbpp_dueling.hip, compiled but not run here)
-static int g_xi[HOST_THREADS];
-static float g_xf[HOST_THREADS];
-
-static inline void __syncthreads() { pthread_barrier_wait(&g_bar); }
-static inline int __shfl_xor(int v, int o) {
-    g_xi[threadIdx.x] = v;
-    pthread_barrier_wait(&g_bar);
-    const int r = g_xi[threadIdx.x ^ o];
-    pthread_barrier_wait(&g_bar);
-    return r;
-}
-static inline float __shfl_xor(float v, int o) {
-    g_xf[threadIdx.x] = v;
-    pthread_barrier_wait(&g_bar);
-    const float r = g_xf[threadIdx.x ^ o];
-    pthread_barrier_wait(&g_bar);
-    return r;
-}
-
-#include "../../irbpp_amd/csrc/irbpp_dueling.hip"
 #include "../../irbpp_amd/csrc/irbpp_dueling_loss.hip"
-
-static_assert(irbpp::DUELING_THREADS == HOST_THREADS, "the harness runs as many threads as the workgroup has");
-
-template <typename F>
-static void run_grid(int gx, int gy, F body) {
-    pthread_barrier_init(&g_bar, nullptr, HOST_THREADS);
-    for (int y = 0; y < gy; ++y)
-        for (int x = 0; x < gx; ++x) {
-            blockIdx.x = (unsigned)x;
-            blockIdx.y = (unsigned)y;
-            std::vector<std::thread> lanes;
-            for (int l = 0; l < HOST_THREADS; ++l)
-                lanes.emplace_back([&, l] { threadIdx.x = (unsigned)l; body(); });
-            for (auto& t : lanes) t.join();
-        }
-    pthread_barrier_destroy(&g_bar);
-}
 
 extern "C" int host_dueling_loss_chunk_rows() { return irbpp::DUELING_LOSS_CHUNK_ROWS; }
 
@@ -72,7 +17,7 @@ extern "C" float host_dueling_dlog(float d) { return irbpp::dueling_dlog(d); }
 
 extern "C" void host_dueling_loss(const float* v, long long v_stride, const float* a, long long env_stride, long long row_stride,
                                   const int64_t* actions, const float* m, int atoms, int s_rows, int batch, float* loss, float* g) {
-    run_grid(batch, 1, [&] {
+    run_grid<irbpp::DUELING_THREADS>(batch, 1, [&] {
         irbpp::irbpp_dueling_loss_kernel(v, v_stride, a, env_stride, row_stride, actions, m, atoms, s_rows, loss, g);
     });
 }
@@ -81,7 +26,7 @@ extern "C" void host_dueling_loss(const float* v, long long v_stride, const floa
 extern "C" void host_dueling_loss_backward(const float* g, const float* grad_loss, const int64_t* actions, int atoms, int s_rows,
                                            int batch, float* grad_v, float* grad_a) {
     const int chunks = grad_a ? (s_rows + irbpp::DUELING_LOSS_CHUNK_ROWS - 1) / irbpp::DUELING_LOSS_CHUNK_ROWS : 1;
-    run_grid(batch, chunks, [&] {
+    run_grid<irbpp::DUELING_THREADS>(batch, chunks, [&] {
         irbpp::irbpp_dueling_loss_backward_kernel(g, grad_loss, actions, atoms, s_rows, grad_v, grad_a);
     });
 }

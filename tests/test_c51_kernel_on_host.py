@@ -4,12 +4,11 @@ kernels' staging, indexing, masking, tie rules and scatter order without a GPU. 
 tests/test_gpu_c51.py, on the small end of its shapes (a workgroup costs 64 host threads here)."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_harness import build_shared
 import test_gpu_c51 as G
 from test_c51_cpu import EPS, act_np, target_np
 
@@ -22,12 +21,7 @@ fp, i64p = C.POINTER(C.c_float), C.POINTER(C.c_int64)
 
 @pytest.fixture(scope="module")
 def host():
-    if shutil.which("g++") is None:
-        pytest.skip("no host compiler")
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-pthread", "-Wno-unused-value",
-                    "-Wno-unknown-pragmas", "-I", os.path.join(HERE, "host", "stub"), SRC, "-o", OUT], check=True)
-    lib = C.CDLL(OUT)
+    lib = C.CDLL(build_shared(SRC, OUT))
     lib.host_c51_act.argtypes = [C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_longlong]
     lib.host_c51_act.restype = None

@@ -5,12 +5,11 @@ resident in the tile / staged in chunks of 256 rows) and the scatter order witho
 layouts as tests/test_gpu_dueling.py, with few workgroups (one costs 512 host threads here)."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_harness import build_shared
 import test_gpu_dueling as G
 from test_dueling_cpu import dueling_act_np, dueling_target_np, f32
 
@@ -22,12 +21,7 @@ LL = C.c_longlong
 
 @pytest.fixture(scope="module")
 def host():
-    if shutil.which("g++") is None:
-        pytest.skip("no host compiler")
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-pthread", "-Wno-unused-value",
-                    "-Wno-unknown-pragmas", "-I", os.path.join(HERE, "host", "stub"), SRC, "-o", OUT], check=True)
-    lib = C.CDLL(OUT)
+    lib = C.CDLL(build_shared(SRC, OUT))
     lib.host_dueling_tile_rows.argtypes = [C.c_int, C.c_int]
     lib.host_dueling_tile_rows.restype = C.c_int
     lib.host_dueling_act.argtypes = [C.c_void_p, LL, C.c_void_p, LL, LL, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,

@@ -7,12 +7,11 @@ of 1 to 3 (a workgroup costs 512 host threads here); the seeds bring every actio
 zero most e into those few samples."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_harness import build_shared
 import test_gpu_dueling_loss as G
 from test_dueling_kernel_on_host import _at, wide_a, wide_v
 from test_dueling_loss_cpu import dlog_np, dueling_loss_backward_np, dueling_loss_np, f32
@@ -25,12 +24,7 @@ LL = C.c_longlong
 
 @pytest.fixture(scope="module")
 def host():
-    if shutil.which("g++") is None:
-        pytest.skip("no host compiler")
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-pthread", "-Wno-unused-value",
-                    "-Wno-unknown-pragmas", "-I", os.path.join(HERE, "host", "stub"), SRC, "-o", OUT], check=True)
-    lib = C.CDLL(OUT)
+    lib = C.CDLL(build_shared(SRC, OUT))
     lib.host_dueling_loss_chunk_rows.restype = C.c_int
     lib.host_dueling_dlog.argtypes = [C.c_float]
     lib.host_dueling_dlog.restype = C.c_float
