@@ -526,6 +526,34 @@ typedef struct {
 int irbpp_replay_gather(const irbpp_replay_view* view, int32_t draws, float beta, const int64_t* data_idx_dev,
                         const float* prob_dev, float* state_dev, int64_t* action_dev, float* return_dev,
                         float* next_state_dev, float* nonterminal_dev, float* weight_dev, void* stream);
+/* The N memories of an irbpp_replay_view sampled as ONE prioritised memory (no reference counterpart: its batch is the
+ * concatenation of per-worker batches, so it cannot be smaller than n_env).  The pooled tree is a top tree over the n_env
+ * row roots -- an implicit heap over P leaves, P the power of two >= n_env, padding 0, rebuilt by every call and never
+ * stored -- with each env's own tree below its leaf; its root T is the pooled total.  Draw j of `draws` (<= 1024) is
+ * v = j*(T/draws) + u*(T/draws), u from the counter-based generator of irbpp_sumtree_sample (its env field a constant no
+ * env uses), walked by `v <= left ? left : (v - left, right)` through the top tree and on, with the residual v, through
+ * that env's tree in global memory (any capacity).  A draw on a padding leaf, one that fails memory.py:175 against its
+ * env's write index, or one of priority 0 is redrawn within its segment up to max_tries times; failed_dev[0] |= 1 if one
+ * stays invalid.  values_dev (may be NULL) float32[draws]: positions in [0, T) used as v directly, looked up once.
+ * Outputs [draws]: env and data / tree index in it (int64), leaf value, and the importance weight of memory.py:199-202 on
+ * the pooled memory: (filled * prob / T)^-beta over the batch maximum, filled = the integer sum over envs of (capacity if
+ * full else index) as float32.  IRBPP_ERR_ARG if n_env > 8192 (the top tree's LDS row). */
+int irbpp_replay_pool_sample(const irbpp_replay_view* view, int32_t draws, const float* values_dev, uint64_t seed,
+                             int32_t max_tries, float beta, int64_t* env_dev, float* prob_dev, int64_t* data_idx_dev,
+                             int64_t* tree_idx_dev, float* weight_dev, int32_t* failed_dev, void* stream);
+/* irbpp_replay_gather for `draws` rows (env_dev[j], data_idx_dev[j]) of a pooled sample: state and next state float32
+ * [draws][obs_len], action int64, n-step return and non-terminal flag float32 [draws].  A row whose env is outside
+ * [0, n_env) is written as zeros. */
+int irbpp_replay_pool_gather(const irbpp_replay_view* view, int32_t draws, const int64_t* env_dev, const int64_t* data_idx_dev,
+                             float* state_dev, int64_t* action_dev, float* return_dev, float* next_state_dev,
+                             float* nonterminal_dev, void* stream);
+/* SegmentTree.update/_propagate (memory.py:47-58) for `count` (<= 1024) triples (env, tree index, priority) applied in
+ * list order: a leaf listed twice keeps its last value, max_dev[env] becomes the maximum of itself and every priority
+ * listed for env, every ancestor of a touched leaf ends as left + right of its final children; nothing else of any row is
+ * read or written (any capacity).  A triple whose env is outside [0, n_env) or whose tree index is no leaf of the row is
+ * ignored.  Priorities are non-negative. */
+int irbpp_replay_pool_update(float* tree_dev, float* max_dev, int32_t n_env, int32_t capacity, const int64_t* env_dev,
+                             const int64_t* tree_idx_dev, const float* priority_dev, int32_t count, void* stream);
 /* The writable side of the same tensor set (memory.py:28-36, 111): int32 timesteps [n_env][capacity], float32 max priority,
  * int32 episode timestep counter [n_env]; the others as in irbpp_replay_view. */
 typedef struct {

@@ -119,6 +119,12 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p]),
     "irbpp_replay_gather": (C.c_int, [C.POINTER(IrbppReplayView), C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "irbpp_replay_pool_sample": (C.c_int, [C.POINTER(IrbppReplayView), C.c_int32, C.c_void_p, C.c_uint64, C.c_int32, C.c_float,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "irbpp_replay_pool_gather": (C.c_int, [C.POINTER(IrbppReplayView), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "irbpp_replay_pool_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int32, C.c_void_p]),
     "irbpp_replay_append": (C.c_int, [C.POINTER(IrbppReplayStore), C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "irbpp_masked_argmax": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,

@@ -8,7 +8,7 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libirbpp_hip.so")
-SOURCES = ["irbpp_capi.hip", "irbpp_kernels.hip", "irbpp_wide.hip", "irbpp_replay.hip", "irbpp_metrics.hip", "irbpp_metrics.h", "irbpp_device.h", "contours_device.h", "irbpp_itemgen.h",
+SOURCES = ["irbpp_capi.hip", "irbpp_kernels.hip", "irbpp_wide.hip", "irbpp_replay.hip", "irbpp_replay_pool.hip", "irbpp_metrics.hip", "irbpp_metrics.h", "irbpp_device.h", "contours_device.h", "irbpp_itemgen.h",
            "irbpp_itemgen.hip", "irbpp_itemgen_device.h", "irbpp_rotalias.h", "irbpp_head.h", "irbpp_c51.hip", "irbpp_dueling.hip", "irbpp_dueling_loss.hip", "irbpp_plan.h", "irbpp_binstate.h", "irbpp_binstate.hip",
            os.path.join("..", "..", "include", "irbpp.h")]
 # -ffp-contract=off: the float64 results must equal numpy's, so no FMA contraction anywhere

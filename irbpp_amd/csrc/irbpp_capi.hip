@@ -21,6 +21,7 @@
 #include "irbpp_kernels.hip"     // single translation unit: kernels + host ABI
 #include "irbpp_wide.hip"         // action grids of 17 .. 32 cells a side: the capacity path
 #include "irbpp_replay.hip"
+#include "irbpp_replay_pool.hip"    // the N memories sampled and updated as one pooled memory (irbpp_replay_pool_sample / _gather / _update)
 #include "irbpp_itemgen.hip"        // the item streams of irbpp_itemgen.h drawn on the device (irbpp_itemgen_dev_*, irbpp_stream_refill)
 #include "irbpp_c51.hip"            // the distributional head around the network (irbpp_categorical_act, irbpp_categorical_target)
 #include "irbpp_dueling.hip"        // the same from the network's logits: dueling combine + softmax fused in (irbpp_dueling_act, irbpp_dueling_target)
@@ -1239,6 +1240,50 @@ int irbpp_replay_append(const irbpp_replay_store* m, const float* state_dev, int
                        m->rewards_dev, m->nonterminals_dev, m->timesteps_dev, m->tree_dev, m->max_dev, m->index_dev, m->full_dev,
                        m->t_dev, m->capacity, m->obs_len, state_dev, (long long)state_stride, action_dev, action_bytes, reward_dev,
                        reward_bytes, terminal_dev, valid_dev);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+static bool replay_view_ok(const irbpp_replay_view* v) {
+    return v && v->states_dev && v->actions_dev && v->rewards_dev && v->nonterminals_dev && v->tree_dev && v->index_dev &&
+           v->full_dev && v->scaling_dev && v->n_env >= 1 && v->capacity >= 1 && v->capacity <= (1 << 30) && v->obs_len >= 1 &&
+           v->n_step >= 1;
+}
+
+int irbpp_replay_pool_sample(const irbpp_replay_view* v, int32_t draws, const float* values_dev, uint64_t seed, int32_t max_tries,
+                             float beta, int64_t* env_dev, float* prob_dev, int64_t* data_idx_dev, int64_t* tree_idx_dev,
+                             float* weight_dev, int32_t* failed_dev, void* stream) {
+    if (!replay_view_ok(v) || draws < 1 || draws > POOL_MAX_DRAWS || max_tries < 1 || !env_dev || !prob_dev || !data_idx_dev ||
+        !tree_idx_dev || !weight_dev || !failed_dev)
+        return IRBPP_ERR_ARG;
+    if (v->n_env > SUMTREE_LDS / 2) return IRBPP_ERR_ARG;            // the top tree over 8192 leaves is the LDS row
+    int top_leaves = 1;
+    while (top_leaves < v->n_env) top_leaves <<= 1;
+    const int floats = 2 * top_leaves - 1 < 8 ? 8 : 2 * top_leaves - 1;
+    hipLaunchKernelGGL(irbpp_replay_pool_sample_kernel, dim3(1), dim3(256), (size_t)floats * sizeof(float), (hipStream_t)stream,
+                       v->tree_dev, v->index_dev, v->full_dev, v->n_env, v->capacity, top_leaves, draws, v->n_step, values_dev, seed,
+                       max_tries, beta, env_dev, prob_dev, data_idx_dev, tree_idx_dev, weight_dev, failed_dev);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+int irbpp_replay_pool_gather(const irbpp_replay_view* v, int32_t draws, const int64_t* env_dev, const int64_t* data_idx_dev,
+                             float* state_dev, int64_t* action_dev, float* return_dev, float* next_state_dev,
+                             float* nonterminal_dev, void* stream) {
+    if (!replay_view_ok(v) || draws < 1 || !env_dev || !data_idx_dev || !state_dev || !action_dev || !return_dev ||
+        !next_state_dev || !nonterminal_dev)
+        return IRBPP_ERR_ARG;
+    hipLaunchKernelGGL(irbpp_replay_pool_gather_kernel, dim3(draws), dim3(256), 0, (hipStream_t)stream, v->states_dev, v->actions_dev,
+                       v->rewards_dev, v->nonterminals_dev, v->scaling_dev, v->n_env, v->capacity, v->obs_len, v->n_step, env_dev,
+                       data_idx_dev, state_dev, action_dev, return_dev, next_state_dev, nonterminal_dev);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+int irbpp_replay_pool_update(float* tree_dev, float* max_dev, int32_t n_env, int32_t capacity, const int64_t* env_dev,
+                             const int64_t* tree_idx_dev, const float* priority_dev, int32_t count, void* stream) {
+    if (!tree_dev || !max_dev || !env_dev || !tree_idx_dev || !priority_dev || n_env < 1 || capacity < 1 || capacity > (1 << 30) ||
+        count < 1 || count > POOL_MAX_DRAWS)
+        return IRBPP_ERR_ARG;
+    hipLaunchKernelGGL(irbpp_replay_pool_update_kernel, dim3(1), dim3((count + 63) / 64 * 64), 0, (hipStream_t)stream, tree_dev,
+                       max_dev, n_env, capacity, env_dev, tree_idx_dev, priority_dev, count);
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
 }
 

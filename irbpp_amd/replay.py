@@ -8,6 +8,8 @@ device tensors and every operation handles all environments at once:
     mem[i].append(state[i], action[i], r[i], d[i])   append(state, action, reward, done, valid)
     mem[i].sample(segment_size)  (agent.py:72-75)    sample(segment_size)  -> env-major batch
     mem[i].update_priorities(idxs[i], loss[...])     update_priorities(tree_idxs, losses)
+    (none: its batch is never smaller than N rows)   sample_pooled(batch_size) -> one batch over all memories as one
+                                                     update_priorities_pooled(idx, losses)   (csrc/irbpp_replay_pool.hip)
 
 Semantics follow memory.py line by line (cited below): cyclic buffer + sum tree per env with
 float32 node sums, new transitions enter with the env's maximum priority, stratified sampling
@@ -72,6 +74,7 @@ class VectorReplayMemory(object):
         # HIP kernels for find / update (one launch each) where the tree row fits their LDS buffer
         self._lib = _hip_lib(self.device) if use_hip in (None, True) else None
         self._append_hip = self._lib is not None              # (irbpp_replay_append walks one leaf's ancestors in global memory: any capacity)
+        self._pool_lib = self._lib                            # (so do the pooled launches: sample_pooled / update_priorities_pooled)
         if use_hip and self._lib is None:
             raise RuntimeError("use_hip=True needs a HIP device")
         if self._lib is not None and 2 * cap - 1 > 16384:
@@ -327,6 +330,187 @@ class VectorReplayMemory(object):
             return
         for j in range(B):
             self._set_leaves(self._rows, tree_idxs[:, j].to(self.device), pr[:, j])
+
+    # ------------------------------------------------------------------ pooled: the N memories as one ----
+    def _view(self):
+        from . import _lib
+        return _lib.IrbppReplayView(
+            states_dev=self.states.data_ptr(), actions_dev=self.actions.data_ptr(), rewards_dev=self.rewards.data_ptr(),
+            nonterminals_dev=self.nonterminals.data_ptr(), tree_dev=self.sum_tree.data_ptr(), index_dev=self.index.data_ptr(),
+            full_dev=self.full.data_ptr(), scaling_dev=self.n_step_scaling.data_ptr(), n_env=self.N, capacity=self.capacity,
+            obs_len=self.obs_len, n_step=self.n)
+
+    def _top_tree(self) -> torch.Tensor:
+        """The implicit heap over P leaves (P the power of two >= N): leaf e is the total of env e, padding 0, every
+        internal node left + right in float32; [0] is the pooled total."""
+        P = 1 << (self.N - 1).bit_length()
+        level = torch.zeros((P,), dtype=torch.float32, device=self.device)
+        level[:self.N] = self.sum_tree[:, 0]
+        levels = [level]
+        while level.numel() > 1:
+            level = level[0::2] + level[1::2]
+            levels.append(level)
+        return torch.cat(levels[::-1])
+
+    def _find_pooled(self, top: torch.Tensor, v: torch.Tensor):
+        """One walk per value of v[B] through the top tree and on, with the residual value, through the env's own tree
+        -> (env, priority, data index, tree index, landed on a padding leaf)."""
+        B, P = v.numel(), (top.numel() + 1) // 2
+        idx = torch.zeros((B,), dtype=torch.int64, device=self.device)
+        v = v.to(device=self.device, dtype=torch.float32).clone()
+        for _ in range(P.bit_length() - 1):
+            lval = top[2 * idx + 1]
+            go_left = v <= lval
+            v = torch.where(go_left, v, v - lval)
+            idx = torch.where(go_left, 2 * idx + 1, 2 * idx + 2)
+        env = idx - (P - 1)
+        padding = env >= self.N
+        env = env.clamp(max=self.N - 1)
+        idx = torch.zeros_like(idx)
+        last = 2 * self.capacity - 2
+        for _ in range(self._depth):
+            left = 2 * idx + 1
+            inner = left <= last
+            lval = self.sum_tree[env, left.clamp(max=last)]
+            go_left = v <= lval
+            v = torch.where(inner & ~go_left, v - lval, v)
+            idx = torch.where(inner, torch.where(go_left, left, left + 1), idx)
+        return env, self.sum_tree[env, idx], idx - (self.capacity - 1), idx, padding
+
+    def _transitions_pooled(self, env: torch.Tensor, data_idx: torch.Tensor):
+        """_get_transition_new (memory.py:123-139) for the rows (env[j], data_idx[j]); the return summed in the order of
+        irbpp_replay_gather_kernel: ret = ret + r * scaling[t]."""
+        pos = data_idx % self.capacity
+        d0 = pos
+        alive = torch.ones_like(pos, dtype=torch.bool)
+        ret = torch.zeros(pos.shape, dtype=torch.float32, device=self.device)
+        for t in range(self.n):
+            r = torch.where(alive, self.rewards[env, pos], torch.zeros((), device=self.device))
+            ret = ret + r * self.n_step_scaling[t]
+            alive = alive & self.nonterminals[env, pos]
+            pos = (pos + 1) % self.capacity
+        last = self.states[env, pos]
+        next_state = torch.where(alive[:, None], last, torch.zeros_like(last))
+        nonterminal = (alive & self.nonterminals[env, pos]).to(torch.float32)
+        return self.states[env, d0], self.actions[env, d0], ret, next_state, nonterminal
+
+    def sample_pooled(self, batch_size: int, values: Optional[torch.Tensor] = None, generator=None, max_tries: int = 64):
+        """One learning batch of ``batch_size`` transitions from the N memories taken as ONE prioritised memory, whatever N
+        is (``batch_size < N`` included): the draws are stratified over the pooled priority mass T -- draw j is
+        ``j * T/B + u * T/B`` -- and walked through a top tree over the N totals and on through that env's own tree; validity
+        (memory.py:175, against that env's write index), n-step transitions and the importance weights of memory.py:199-202
+        (``filled`` the transitions held by all envs together, normalised by the batch maximum) as in ``sample``.
+
+        ``values`` (optional, [B]) are positions in [0, T) looked up as they are (ValueError if one is invalid); otherwise
+        invalid draws are redrawn within their segment up to ``max_tries`` times (RuntimeError after that).
+        Returns (idx int64 [B, 2] = (env, tree_idx), states, actions, returns, next_states, nonterminals [B, 1], weights):
+        the tuple shape of ``sample``, so ``learn_loss`` takes it unchanged; ``update_priorities_pooled`` takes ``idx``."""
+        B, dev = int(batch_size), self.device
+        if B < 1:
+            raise ValueError("batch_size must be at least 1")
+        if values is not None:
+            values = values.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+            if values.numel() != B:
+                raise ValueError(f"values must hold {B} positions")
+        if self._pool_lib is not None and self.states.dtype == torch.float32:
+            from . import _lib
+            lib, view = self._pool_lib, self._view()
+            seed = 0
+            if values is None:
+                gdev = "cpu" if generator is None else generator.device
+                seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator, device=gdev).item())
+            env = torch.empty((B,), dtype=torch.int64, device=dev)
+            prob = torch.empty((B,), dtype=torch.float32, device=dev)
+            data_idx = torch.empty((B,), dtype=torch.int64, device=dev)
+            tree_idx = torch.empty((B,), dtype=torch.int64, device=dev)
+            we = torch.empty((B,), dtype=torch.float32, device=dev)
+            failed = torch.zeros((1,), dtype=torch.int32, device=dev)
+            _lib.check(lib.irbpp_replay_pool_sample(C.byref(view), B, _p(values), seed, int(max_tries), float(self.priority_weight),
+                                                    _p(env), _p(prob), _p(data_idx), _p(tree_idx), _p(we), _p(failed), _stream(dev)),
+                       "irbpp_replay_pool_sample")
+            if int(failed.item()):                                 # the one host round trip, as in sample()
+                if values is not None:
+                    raise ValueError("a supplied sample position is invalid (memory.py:175)")
+                raise RuntimeError("could not draw a valid sample from every segment; append more transitions first")
+            st = torch.empty((B, self.obs_len), dtype=torch.float32, device=dev)
+            nx = torch.empty((B, self.obs_len), dtype=torch.float32, device=dev)
+            ac = torch.empty((B,), dtype=torch.int64, device=dev)
+            re = torch.empty((B,), dtype=torch.float32, device=dev)
+            nt = torch.empty((B, 1), dtype=torch.float32, device=dev)
+            _lib.check(lib.irbpp_replay_pool_gather(C.byref(view), B, _p(env), _p(data_idx), _p(st), _p(ac), _p(re), _p(nx), _p(nt),
+                                                    _stream(dev)), "irbpp_replay_pool_gather")
+            return torch.stack([env, tree_idx], dim=1), st, ac, re, nx, nt, we
+        top = self._top_tree()
+        p_total = top[0]
+        w = self.index
+
+        def lookup(v):
+            env, prob, data_idx, tree_idx, padding = self._find_pooled(top, v)
+            ok = (((w[env] - data_idx) % self.capacity > self.n) & ((data_idx - w[env]) % self.capacity >= 1) & (prob != 0) &
+                  ~padding)
+            return env, prob, data_idx, tree_idx, ok
+
+        if values is not None:
+            env, prob, data_idx, tree_idx, ok = lookup(values)
+            if not bool(ok.all()):
+                raise ValueError("a supplied sample position is invalid (memory.py:175)")
+        else:
+            segment = p_total / B
+            lo = torch.arange(B, device=dev, dtype=torch.float32) * segment
+            draw = lambda: lo + torch.rand((B,), device=dev, generator=generator) * segment  # noqa: E731
+            env, prob, data_idx, tree_idx, ok = lookup(draw())
+            for _ in range(int(max_tries) - 1):
+                if bool(ok.all()):
+                    break
+                e2, p2, d2, t2, ok2 = lookup(draw())
+                env, prob, data_idx, tree_idx = (torch.where(ok, a, b) for a, b in ((env, e2), (prob, p2), (data_idx, d2), (tree_idx, t2)))
+                ok = ok | ok2
+            if not bool(ok.all()):
+                raise RuntimeError("could not draw a valid sample from every segment; append more transitions first")
+        state, action, returns, next_state, nonterminal = self._transitions_pooled(env, data_idx)
+        filled = torch.where(self.full, torch.full_like(self.index, self.capacity), self.index).sum().to(torch.float32)
+        weights = (filled * (prob / p_total)) ** -self.priority_weight                # memory.py:199-201 on the pooled memory
+        weights = weights / weights.max()                                             # (:202) over the batch
+        return (torch.stack([env, tree_idx], dim=1), state.to(torch.float32), action, returns, next_state.to(torch.float32),
+                nonterminal.reshape(B, 1), weights)
+
+    def update_priorities_pooled(self, idx: torch.Tensor, priorities: torch.Tensor, powered: bool = False) -> None:
+        """``update_priorities`` for the rows of a pooled batch: ``idx`` int64 [B, 2] = (env, tree_idx) as ``sample_pooled``
+        returns it, ``priorities`` [B]; priority^omega (``powered=True``: the values already are) goes into the listed
+        leaves in list order, so a leaf listed twice keeps its last value, each env's maximum priority takes in every value
+        listed for it, and every ancestor of a touched leaf ends as left + right.  Only those leaves and their ancestors are
+        touched.  A row whose tree_idx is no leaf or whose env is outside [0, N) is ignored."""
+        dev = self.device
+        idx = idx.to(device=dev, dtype=torch.int64).reshape(-1, 2)
+        B = idx.shape[0]
+        pr = priorities.to(dev, torch.float32).reshape(B)
+        if not powered:
+            pr = torch.pow(pr, self.priority_exponent)
+        env, ti = idx[:, 0].contiguous(), idx[:, 1].contiguous()
+        if self._pool_lib is not None:
+            from . import _lib
+            _lib.check(self._pool_lib.irbpp_replay_pool_update(_p(self.sum_tree), _p(self.max), self.N, self.capacity, _p(env), _p(ti),
+                                                               _p(pr.contiguous()), B, _stream(dev)), "irbpp_replay_pool_update")
+            return
+        cap = self.capacity
+        keep = (env >= 0) & (env < self.N) & (ti >= cap - 1) & (ti <= 2 * cap - 2)
+        env, ti, pr = env[keep], ti[keep], pr[keep]
+        if env.numel() == 0:
+            return
+        self.max.scatter_reduce_(0, env, pr, reduce="amax", include_self=True)        # overwritten duplicates included
+        key = env * (2 * cap - 1) + ti
+        live = ~torch.triu(key[:, None] == key[None, :], diagonal=1).any(dim=1)       # no later triple names the same leaf
+        env, node, pr = env[live], ti[live], pr[live]
+        self.sum_tree[env, node] = pr
+        # ancestors by actual depth floor(log2(idx + 1)), deepest level first (a capacity that is no power of two has its
+        # leaves at two depths); rows that meet at a node write the same sum of the same final children
+        depth = torch.floor(torch.log2((node + 1).to(torch.float64))).to(torch.int64)
+        for d in range((2 * cap - 1).bit_length() - 1, 0, -1):
+            at = depth == d
+            node = torch.where(at, (node - 1) // 2, node)
+            e, i = env[at], node[at]
+            self.sum_tree[e, i] = self.sum_tree[e, 2 * i + 1] + self.sum_tree[e, 2 * i + 2]
+            depth = torch.where(at, depth - 1, depth)
 
     def anneal(self, increase: float) -> None:
         """trainer.py:195-196."""
