@@ -647,6 +647,42 @@ int irbpp_dueling_loss(const float* v_dev, int64_t v_stride, const float* a_dev,
 int irbpp_dueling_loss_backward(const float* g_dev, const float* grad_loss_dev, const int64_t* actions_dev, int32_t atoms,
                                 int32_t s_rows, int32_t batch, float* grad_v_out_dev, float* grad_a_out_dev, void* stream);
 
+/* The four effective layers of the value and advantage streams (model.py:393-394: fc_h_v, fc_z_v, fc_h_a, fc_z_a), float32 on
+ * the device, row-major [out][in] and contiguous: w_hv [hidden][embed], w_zv [atoms][hidden], w_ha [hidden][embed],
+ * w_za [atoms][hidden], each bias [out].  In training mode they are what irbpp_noisy_weights writes; in eval mode the mu
+ * tensors as they are. */
+typedef struct { const float *w_hv, *b_hv, *w_zv, *b_zv, *w_ha, *b_ha, *w_za, *b_za;   /* effective, row-major [out][in] */
+                 int32_t embed, hidden, atoms; } irbpp_stream_weights;
+/* replaces: NoisyLinear.forward's weight_mu + weight_sigma * weight_epsilon and the same for the bias (model.py, training
+ * mode), for one layer: w_out[j][k] = mu[j][k] + sigma[j][k] * eps[j][k] and b_out[j] = bias_mu[j] + bias_sigma[j] *
+ * bias_eps[j], the multiply and the add rounded separately: torch's two elementwise ops, bit for bit.  All arrays float32 on
+ * the device and contiguous: [out][in] and [out].  Call it after every reset_noise, once per layer.
+ * IRBPP_ERR_ARG unless 1 <= out, in <= 256 and no pointer is NULL. */
+int irbpp_noisy_weights(const float* mu, const float* sigma, const float* eps, const float* bias_mu, const float* bias_sigma,
+                        const float* bias_eps, int32_t out, int32_t in, float* w_out, float* b_out, void* stream);
+/* replaces: the last stage of DQNBPP.forward (model.py:393-400: the value stream fc_z_v(relu(fc_h_v(xGlobal))), the advantage
+ * stream fc_z_a(relu(fc_h_a(x))), v + a - a.mean(1), softmax over the atoms) and all of Agent.act after it (agent.py:51-58) in
+ * one launch from the embeddings: neither the [n_env][s_rows][hidden] hidden block nor the advantage logits reach memory
+ * unless a_out_dev asks for them.  xg_dev float32 [n_env][embed], rows xg_stride floats apart; x_dev float32
+ * [n_env][s_rows][embed], row r of env e at x_dev + e*env_stride + r*row_stride; support, obs, q_out as in
+ * irbpp_dueling_act; action_dev int64[n_env], may be NULL when only logits are wanted (with q_out_dev NULL too nothing
+ * after the logits is computed).  v_out_dev (may be NULL) float32 [n_env][atoms] and a_out_dev (may be NULL) float32
+ * [n_env][s_rows][atoms], contiguous: the logits irbpp_dueling_target consumes.  The float32 arithmetic is defined
+ * (csrc/irbpp_streams.hip): every output of a layer is one chain acc = b[j]; acc = fmaf(x[k], W[j][k], acc) for k ascending,
+ * a single-rounding fused multiply-add, never split or re-associated; relu(s) = s > 0 ? s : +0; from (v, a) on the
+ * arithmetic of irbpp_dueling_act.  Reproducible bit for bit whatever n_env, the strides and the block's size.  Where
+ * s_rows * (atoms | 1) * 4 exceeds the 144 KB LDS tile of irbpp_dueling_act, a_out_dev is required as workspace (the logits
+ * go to memory and a second launch takes irbpp_dueling_act's path over them: the same bits).  Inputs must be finite: a NaN
+ * or an infinity gives unspecified values, the action is still a row index in [0, s_rows) and nothing is accessed out of
+ * range.  IRBPP_ERR_ARG unless 1 <= embed, hidden <= 256, 2 <= atoms <= 128, 1 <= s_rows <= 1024, n_env >= 1,
+ * xg_stride >= embed, row_stride >= embed, env_stride >= (s_rows-1)*row_stride + embed, obs_stride >= 5*s_rows,
+ * q_stride >= s_rows, support_dev given with action_dev or q_out_dev, at least one output, and a_out_dev where the block
+ * does not fit. */
+int irbpp_streams_act(const irbpp_stream_weights* w, const float* xg_dev, int64_t xg_stride, const float* x_dev,
+                      int64_t env_stride, int64_t row_stride, const float* support_dev, const float* obs_dev, int32_t obs_stride,
+                      int32_t s_rows, int32_t n_env, int64_t* action_dev /* may be NULL when only logits are wanted */,
+                      float* q_out_dev, int64_t q_stride, float* v_out_dev, float* a_out_dev, void* stream);
+
 /* Tooling: when cycles_dev != NULL every later transition launch stores, per bin, one row
  * int64[num_bins][16]: shader-clock stamps 0 start, 1 action applied, 2 overlap test done,
  * 3 contour stage done, 4 observation written; 5..7 contour-stage detail; 8/9 the 100 MHz wall

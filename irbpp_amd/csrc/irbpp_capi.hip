@@ -26,6 +26,7 @@
 #include "irbpp_c51.hip"            // the distributional head around the network (irbpp_categorical_act, irbpp_categorical_target)
 #include "irbpp_dueling.hip"        // the same from the network's logits: dueling combine + softmax fused in (irbpp_dueling_act, irbpp_dueling_target)
 #include "irbpp_dueling_loss.hip"   // the loss that carries the gradient, forward and backward from the logits (irbpp_dueling_loss, irbpp_dueling_loss_backward)
+#include "irbpp_streams.hip"        // the four noisy layers of the value and advantage streams in front of the dueling head (irbpp_noisy_weights, irbpp_streams_act)
 #include "irbpp_metrics.hip"        // the trainer's episode metrics (irbpp_set_episode_window)
 #include "irbpp_itemgen.h"
 #include "irbpp_plan.h"             // which kernels a transition launches: the registry of kernels and plan_transition
@@ -1210,6 +1211,47 @@ int irbpp_dueling_loss_backward(const float* g_dev, const float* grad_loss_dev, 
     const int chunks = grad_a_out_dev ? (s_rows + DUELING_LOSS_CHUNK_ROWS - 1) / DUELING_LOSS_CHUNK_ROWS : 1;
     hipLaunchKernelGGL(irbpp_dueling_loss_backward_kernel, dim3(batch, chunks), dim3(DUELING_THREADS), 0, (hipStream_t)stream,
                        g_dev, grad_loss_dev, actions_dev, atoms, s_rows, grad_v_out_dev, grad_a_out_dev);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+int irbpp_noisy_weights(const float* mu, const float* sigma, const float* eps, const float* bias_mu, const float* bias_sigma,
+                        const float* bias_eps, int32_t out, int32_t in, float* w_out, float* b_out, void* stream) {
+    if (!mu || !sigma || !eps || !bias_mu || !bias_sigma || !bias_eps || !w_out || !b_out || out < 1 || in < 1 ||
+        out > STREAMS_MAX_WIDTH || in > STREAMS_MAX_WIDTH)
+        return IRBPP_ERR_ARG;
+    hipLaunchKernelGGL(irbpp_noisy_weights_kernel, dim3((out * in + 255) / 256), dim3(256), 0, (hipStream_t)stream, mu, sigma, eps,
+                       bias_mu, bias_sigma, bias_eps, out, in, w_out, b_out);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+int irbpp_streams_act(const irbpp_stream_weights* w, const float* xg_dev, int64_t xg_stride, const float* x_dev, int64_t env_stride,
+                      int64_t row_stride, const float* support_dev, const float* obs_dev, int32_t obs_stride, int32_t s_rows,
+                      int32_t n_env, int64_t* action_dev, float* q_out_dev, int64_t q_stride, float* v_out_dev, float* a_out_dev,
+                      void* stream) {
+    if (!w || !w->w_hv || !w->b_hv || !w->w_zv || !w->b_zv || !w->w_ha || !w->b_ha || !w->w_za || !w->b_za || w->embed < 1 ||
+        w->embed > STREAMS_MAX_WIDTH || w->hidden < 1 || w->hidden > STREAMS_MAX_WIDTH || w->atoms < 2 ||
+        w->atoms > HEAD_MAX_ATOMS || s_rows < 1 || s_rows > HEAD_MAX_ROWS || n_env < 1 || !xg_dev || xg_stride < w->embed ||
+        !x_dev || row_stride < w->embed || env_stride < (int64_t)(s_rows - 1) * row_stride + w->embed ||
+        (obs_dev && obs_stride < 5 * s_rows) || (q_out_dev && q_stride < s_rows) || ((action_dev || q_out_dev) && !support_dev) ||
+        (!action_dev && !q_out_dev && !v_out_dev && !a_out_dev))
+        return IRBPP_ERR_ARG;
+    const bool resident = dueling_tile_rows(s_rows, w->atoms) == s_rows;
+    if (!resident && !a_out_dev) return IRBPP_ERR_ARG;                         // the block needs a_out as its workspace
+    StreamsArgs g;
+    g.xg_stride = xg_stride, g.env_stride = env_stride, g.row_stride = row_stride, g.q_stride = q_stride;
+    g.embed = w->embed, g.hidden = w->hidden, g.atoms = w->atoms, g.obs_stride = obs_stride, g.s_rows = s_rows;
+    g.x_vec4 = ((uintptr_t)x_dev % 16 == 0 && (uintptr_t)w->w_ha % 16 == 0 && env_stride % 4 == 0 && row_stride % 4 == 0 && w->embed % 4 == 0) ? 1 : 0;
+    const auto kernel = w->atoms <= 32 ? irbpp_streams_act_a32_kernel : irbpp_streams_act_kernel;
+    size_t lds = 0;
+    if (resident && !dueling_lds((const void*)kernel, w->atoms, s_rows, &lds)) return IRBPP_ERR_HIP;
+    hipLaunchKernelGGL(kernel, dim3(n_env), dim3(DUELING_THREADS), lds, (hipStream_t)stream, w->w_hv, w->b_hv, w->w_zv, w->b_zv,
+                       w->w_ha, w->b_ha, w->w_za, w->b_za, xg_dev, x_dev, support_dev, obs_dev, action_dev, q_out_dev, v_out_dev,
+                       a_out_dev, g);
+    if (hipGetLastError() != hipSuccess) return IRBPP_ERR_HIP;
+    if (resident || (!action_dev && !q_out_dev)) return IRBPP_OK;
+    if (!dueling_lds((const void*)irbpp_streams_finish_kernel, w->atoms, s_rows, &lds)) return IRBPP_ERR_HIP;
+    hipLaunchKernelGGL(irbpp_streams_finish_kernel, dim3(n_env), dim3(DUELING_THREADS), lds, (hipStream_t)stream, w->w_hv, w->b_hv,
+                       w->w_zv, w->b_zv, xg_dev, (const float*)a_out_dev, support_dev, obs_dev, action_dev, q_out_dev, g);
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
 }
 

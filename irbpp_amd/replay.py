@@ -849,6 +849,178 @@ def learn_loss(online_logits, target_logits, batch, support: torch.Tensor, gamma
     return dueling_c51_loss(v, a, actions, m, use_hip=use_hip)
 
 
+# The same question for the streams in front of the dueling head ("The noisy streams"): torch's layers
+# followed by dueling_greedy_action, since tools/streams_rates.py measured them on an MI355X at 1.79 ms against 5.76 ms for the
+# fused call at 4096 envs and 0.47 ms against 1.46 ms at 1024 (profiles/noisy_streams/): the matrix units win over the defined
+# fmaf chain.  use_hip=True asks for the kernels (the reproducible forward).
+STREAMS_HIP_DEFAULT = False
+
+STREAMS_MAX_WIDTH, STREAMS_MAX_ATOMS, STREAMS_MAX_ROWS = 256, 128, 1024
+_STREAM_LAYERS = ("fc_h_v", "fc_z_v", "fc_h_a", "fc_z_a")
+
+
+class _IrbppStreamWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("w_hv", "b_hv", "w_zv", "b_zv", "w_ha", "b_ha", "w_za", "b_za")] + \
+               [("embed", C.c_int32), ("hidden", C.c_int32), ("atoms", C.c_int32)]
+
+
+def _fmaf_np(a, b, c):
+    """fmaf on float32 numpy arrays, exactly: the product of two float32 is exact in float64; the float64 sum is brought to
+    round-to-odd by its TwoSum error, which makes the final rounding to float32 the single rounding of the exact value."""
+    import numpy as np
+    with np.errstate(all="ignore"):
+        p = a.astype(np.float64) * b.astype(np.float64)
+        c = np.broadcast_to(c, p.shape).astype(np.float64)
+        s = p + c
+        bb = s - p
+        err = (p - (s - bb)) + (c - bb)
+        bits = s.view(np.int64)
+        fix = (err != 0) & ((bits & 1) == 0) & np.isfinite(s)
+        step = np.where((err > 0) == (s > 0), 1, -1)
+        return np.where(fix, bits + step, bits).view(np.float64).astype(np.float32)
+
+
+def _lin_np(w, b, x):
+    """The defined linear layer on float32 numpy arrays: x [..., K], w [J, K], b [J] -> [..., J], one fmaf chain per output."""
+    import numpy as np
+    acc = np.broadcast_to(b, x.shape[:-1] + b.shape).astype(np.float32)
+    for k in range(w.shape[1]):
+        acc = _fmaf_np(x[..., k:k + 1], w[:, k], acc)
+    return acc
+
+
+def _streams_logits_cpu(x: torch.Tensor, xg: torch.Tensor, w: "StreamWeights") -> Tuple[torch.Tensor, torch.Tensor]:
+    import numpy as np
+    relu = lambda t: np.where(t > 0, t, np.float32(0))   # noqa: E731
+    n = lambda t: t.detach().to(torch.float32).cpu().numpy()  # noqa: E731
+    v = _lin_np(n(w.w_zv), n(w.b_zv), relu(_lin_np(n(w.w_hv), n(w.b_hv), n(xg))))
+    a = _lin_np(n(w.w_za), n(w.b_za), relu(_lin_np(n(w.w_ha), n(w.b_ha), n(x))))
+    return torch.from_numpy(np.ascontiguousarray(v)), torch.from_numpy(np.ascontiguousarray(a))
+
+
+class StreamWeights(object):
+    """The four effective layers of DQNBPP's value and advantage streams (model.py:393-394) as float32 device tensors, row-major
+    [out][in]: what streams_greedy_action / streams_logits multiply by.  Built from any four objects that expose
+    ``weight_mu / weight_sigma / weight_epsilon / bias_mu / bias_sigma / bias_epsilon`` (the reference's NoisyLinear): with
+    ``training=True`` the effective weights are ``mu + sigma * epsilon`` (irbpp_noisy_weights on a HIP device, torch's two ops
+    on the CPU: the same bits), with ``training=False`` the ``mu`` tensors as they are.  Call ``refresh()`` after every
+    ``reset_noise`` (and after every optimiser step that changes mu or sigma)."""
+
+    def __init__(self, fc_h_v, fc_z_v, fc_h_a, fc_z_a, training: bool = True):
+        self.layers = (fc_h_v, fc_z_v, fc_h_a, fc_z_a)
+        self.training = bool(training)
+        self.hidden, self.embed = (int(d) for d in fc_h_v.weight_mu.shape)
+        self.atoms = int(fc_z_v.weight_mu.shape[0])
+        want = [(self.hidden, self.embed), (self.atoms, self.hidden), (self.hidden, self.embed), (self.atoms, self.hidden)]
+        for name, layer, shape in zip(_STREAM_LAYERS, self.layers, want):
+            if tuple(layer.weight_mu.shape) != shape or tuple(layer.bias_mu.shape) != shape[:1]:
+                raise ValueError(f"{name}: weight_mu {tuple(layer.weight_mu.shape)} beside the expected {shape}")
+        if not (1 <= self.embed <= STREAMS_MAX_WIDTH and 1 <= self.hidden <= STREAMS_MAX_WIDTH and
+                2 <= self.atoms <= STREAMS_MAX_ATOMS):
+            raise ValueError("streams: 1 <= embed, hidden <= 256 and 2 <= atoms <= 128")
+        self.device = fc_h_v.weight_mu.device
+        self.refresh()
+
+    @classmethod
+    def from_layers(cls, fc_h_v, fc_z_v, fc_h_a, fc_z_a, training: bool = True) -> "StreamWeights":
+        return cls(fc_h_v, fc_z_v, fc_h_a, fc_z_a, training)
+
+    @torch.no_grad()
+    def refresh(self) -> "StreamWeights":
+        lib = _hip_lib(self.device)
+        out = []
+        for layer in self.layers:
+            t = [_f32(getattr(layer, n).detach(), self.device) for n in ("weight_mu", "weight_sigma", "weight_epsilon", "bias_mu",
+                                                                         "bias_sigma", "bias_epsilon")]
+            if not self.training:
+                out += [t[0].clone(), t[3].clone()]
+            elif lib is None:
+                out += [t[0] + t[1] * t[2], t[3] + t[4] * t[5]]
+            else:
+                from . import _lib
+                w, b = torch.empty_like(t[0]), torch.empty_like(t[3])
+                _lib.check(lib.irbpp_noisy_weights(*(_p(x) for x in t), t[0].shape[0], t[0].shape[1], _p(w), _p(b),
+                                                   _stream(self.device)), "irbpp_noisy_weights")
+                out += [w, b]
+        self.w_hv, self.b_hv, self.w_zv, self.b_zv, self.w_ha, self.b_ha, self.w_za, self.b_za = out
+        return self
+
+    def _struct(self) -> _IrbppStreamWeights:
+        return _IrbppStreamWeights(*(x.data_ptr() for x in (self.w_hv, self.b_hv, self.w_zv, self.b_zv, self.w_ha, self.b_ha, self.w_za,
+                                                            self.b_za)), self.embed, self.hidden, self.atoms)
+
+
+def _streams_inputs(x: torch.Tensor, x_global: torch.Tensor, w: StreamWeights) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x [N, S, E] and x_global [N, E] (or [N, 1, E]) as float32 with contiguous rows, slices as they are; limits checked."""
+    if x.dim() != 3 or x.shape[2] != w.embed:
+        raise ValueError(f"x must be [N, S, {w.embed}]")
+    N, S, _ = x.shape
+    if x_global.dim() == 3 and x_global.shape[1] == 1:
+        x_global = x_global[:, 0]
+    if tuple(x_global.shape) != (N, w.embed):
+        raise ValueError(f"x_global must be [{N}, {w.embed}] (or [{N}, 1, {w.embed}]) beside x {tuple(x.shape)}")
+    if not (N >= 1 and 1 <= S <= STREAMS_MAX_ROWS):
+        raise ValueError("streams: N >= 1 and 1 <= S <= 1024")
+    return _c51_block(x), _dueling_v(x_global)
+
+
+def _streams_call(lib, x, xg, w, support, state, q_out, want_action, want_logits):
+    from . import _lib
+    N, S, _ = x.shape
+    dev = x.device
+    fits = S * (w.atoms | 1) * 4 <= 144 * 1024           # DUELING_TILE_BYTES: a larger block needs a_out as its workspace
+    state, obs_stride = _obs_arg(state)
+    q_stride = _q_out_arg(q_out, N, S, dev, "x")
+    action = torch.empty((N,), dtype=torch.int64, device=dev) if want_action else None
+    v = torch.empty((N, w.atoms), dtype=torch.float32, device=dev) if want_logits else None
+    a = torch.empty((N, S, w.atoms), dtype=torch.float32, device=dev) if want_logits or not fits else None
+    ws = w._struct()
+    _lib.check(lib.irbpp_streams_act(C.byref(ws), _p(xg), xg.stride(0), _p(x), x.stride(0), x.stride(1), _p(support), _p(state),
+                                     obs_stride, S, N, _p(action), _p(q_out), q_stride, _p(v), _p(a), _stream(dev)),
+               "irbpp_streams_act")
+    return action, v, a
+
+
+@torch.no_grad()
+def streams_greedy_action(x: torch.Tensor, x_global: torch.Tensor, weights: StreamWeights, support: torch.Tensor,
+                          state: Optional[torch.Tensor] = None, *, q_out: Optional[torch.Tensor] = None,
+                          use_hip: Optional[bool] = None) -> torch.Tensor:
+    """The last stage of DQNBPP.forward (model.py:393-400: the four noisy layers of the value and advantage streams, the
+    combine and the softmax) and all of Agent.act after it (agent.py:51-58), from the embeddings ``x`` [N, S, E] and
+    ``x_global`` [N, E] (or [N, 1, E]) -> int64[N].  ``weights``: a StreamWeights; ``support`` / ``state`` / ``q_out`` as in
+    dueling_greedy_action.  With ``use_hip=True`` (a HIP device; ``None`` takes STREAMS_HIP_DEFAULT) one kernel does all of it
+    in a defined float32 arithmetic (irbpp_streams_act: every layer output one ascending fmaf chain, then the arithmetic of
+    irbpp_dueling_act; neither the hidden block nor the logits reach memory).  Otherwise the same definition runs in two steps:
+    streams_logits (on the CPU an exact numpy emulation of the chains, on a HIP device torch's layers) and
+    dueling_greedy_action."""
+    x, xg = _streams_inputs(x, x_global, weights)
+    lib = _head_lib(x, use_hip, STREAMS_HIP_DEFAULT)
+    if lib is None:
+        v, a = streams_logits(x, xg, weights, use_hip=False)
+        return dueling_greedy_action(v, a, support, state, None, q_out, use_hip=None if x.is_cuda else False)
+    return _streams_call(lib, x, xg, weights, _f32(support, x.device), state, q_out, True, False)[0]
+
+
+@torch.no_grad()
+def streams_logits(x: torch.Tensor, x_global: torch.Tensor, weights: StreamWeights, *,
+                   use_hip: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The value and advantage streams alone, without a gradient: -> (v float32 [N, atoms], a float32 [N, S, atoms]), what
+    dueling_c51_target consumes (the two no_grad network calls of Agent.learn, agent.py:90, 96).  Forms as in
+    streams_greedy_action; on a HIP device without the kernels torch's ``F.linear`` / ``relu`` lines run (rocBLAS's own
+    summation order: close to, not bit-equal with, the definition)."""
+    x, xg = _streams_inputs(x, x_global, weights)
+    lib = _head_lib(x, use_hip, STREAMS_HIP_DEFAULT)
+    if lib is not None:
+        _, v, a = _streams_call(lib, x, xg, weights, None, None, None, False, True)
+        return v, a
+    if x.is_cuda:
+        F = torch.nn.functional
+        w = weights
+        return (F.linear(F.relu(F.linear(xg, w.w_hv, w.b_hv)), w.w_zv, w.b_zv),
+                F.linear(F.relu(F.linear(x, w.w_ha, w.b_ha)), w.w_za, w.b_za))
+    return _streams_logits_cpu(x, xg, weights)
+
+
 def actor_step(envs, policy, memory: VectorReplayMemory, state: torch.Tensor, reward_clip: float = 0.0):
     """One iteration of the trainer's acting loop (trainer.py:160-186) without per-env Python:
     mask -> policy -> envs.step -> clip -> append.  ``envs`` is a GpuPackingEnv (device-tensor
