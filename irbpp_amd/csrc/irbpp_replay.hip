@@ -91,7 +91,7 @@ constexpr int SUMTREE_LDS = 16384;                       // floats: capacities u
 extern "C" __global__ void __launch_bounds__(64)
 irbpp_sumtree_update_kernel(float* __restrict__ tree, float* __restrict__ maxp, int cap, const int64_t* __restrict__ tree_idx,
                             const float* __restrict__ prio, int b, const uint8_t* __restrict__ row_mask) {
-    extern __shared__ float row[];                       // 2*cap - 1 floats (dynamic: a 64-transition ring needs 508 bytes, not 64 KB)
+    HIP_DYNAMIC_SHARED(float, row)                       // 2*cap - 1 floats (dynamic: a 64-transition ring needs 508 bytes, not 64 KB)
     const int env = blockIdx.x, lane = threadIdx.x;
     if (row_mask && !row_mask[env]) return;              // append() of a subset of the envs
     const int len = 2 * cap - 1;

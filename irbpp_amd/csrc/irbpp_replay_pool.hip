@@ -25,7 +25,7 @@ irbpp_replay_pool_sample_kernel(const float* __restrict__ tree, const int64_t* _
                                 int max_tries, float beta, int64_t* __restrict__ env_out, float* __restrict__ prob,
                                 int64_t* __restrict__ data_idx, int64_t* __restrict__ tree_idx, float* __restrict__ weight,
                                 int32_t* __restrict__ failed) {
-    extern __shared__ float top[];
+    HIP_DYNAMIC_SHARED(float, top)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int len = 2 * cap - 1, top_len = 2 * top_leaves - 1;
     // filled: the integer sum over envs of (capacity if full else index), converted once

@@ -475,3 +475,104 @@ def test_masked_argmax_shapes_strides_ties_and_infinities(s):
         got = out.cpu().numpy()
         np.testing.assert_array_equal(got[:n], want, err_msg=f"S={s} n_env={n}")
         assert got[n] == -7                                                 # the partial last workgroup wrote nothing past n_env
+
+
+# ------------------------------------------------------------------ the generator's known answers ----------------------------
+M64 = (1 << 64) - 1
+POOL_RNG_ENV = 0xFFFFFFFF                                                  # uniform01's env field for pooled draws
+
+
+def uniform01(seed, env, j, attempt):
+    """The counter-based generator of csrc/irbpp_replay.hip in Python integers, from its text: splitmix64's finaliser over
+    seed + golden * ((env << 32) ^ (j << 8) ^ attempt ^ constant), all modulo 2^64 (env, j and attempt 32-bit fields), the top
+    24 bits as a float32 in [0, 1)."""
+    counter = ((env << 32) ^ (j << 8) ^ attempt ^ 0xD1B54A32D192ED03) & M64
+    z = (seed + 0x9E3779B97F4A7C15 * counter) & M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+    z ^= z >> 31
+    u = f32(z >> 40) * f32(1.0 / 16777216.0)
+    assert u.dtype == f32 and 0.0 <= u < 1.0
+    return u
+
+
+KA_CAP, KA_STEP, KA_TRIES = 8192, 3, 16
+
+
+def _known_answer_tree():
+    """A full ring of 8192 leaves, odd leaves of priority 1 and even ones 0: every node an integer, the total 4096.  With one
+    draw per env lo = 0 and v = u * 4096 is exact whether the compiler fuses lo + u * segment or not."""
+    leaves = np.zeros((1, KA_CAP), dtype=f32)
+    leaves[0, 1::2] = 1.0
+    tree = rebuild(leaves)[0]
+    assert tree[0] == 4096.0 and (tree == np.round(tree)).all()
+    return tree
+
+
+def _known_answer_walk(tree, env_field, seed, w, first=0):
+    """-> (leaf, priority, attempts used): attempts first, first + 1, ... until the reference's validity test (memory.py:175)
+    holds against the write index w."""
+    oracle = _oracle_tree(tree, KA_CAP)
+    for attempt in range(first, KA_TRIES):
+        v = f32(uniform01(seed, env_field, 0, attempt) * tree[0])
+        p, d, t = oracle.find(v)
+        if (w - d) % KA_CAP > KA_STEP and (d - w) % KA_CAP >= 1 and p != 0:
+            return t, p, attempt + 1
+    raise AssertionError("fixture: no valid draw")
+
+
+@pytest.mark.parametrize("n", [1, 257])
+def test_sumtree_sample_draws_the_generators_leaf(n):
+    """irbpp_sumtree_sample's leaf is the one the Python-integer generator and the model's walk give, env by env.  Every
+    fourth env has its write index on the leaf of its first attempt, so that draw is refused and the answer depends on
+    `attempt` entering the counter."""
+    L, lib = _lib()
+    seed = 0x8000000000000000 | 20261019
+    tree = _known_answer_tree()
+    w = np.array([(e * 37) % KA_CAP for e in range(n)], dtype=np.int64)
+    for e in range(0, n, 4):
+        first = _oracle_tree(tree, KA_CAP).find(f32(uniform01(seed, e, 0, 0) * tree[0]))
+        w[e] = first[1]
+    want = [_known_answer_walk(tree, e, seed, int(w[e])) for e in range(n)]
+    assert max(a for _, _, a in want) > 1                                 # some env needs more than one attempt
+    trees, index = _dev(np.tile(tree, (n, 1))), _dev(w)
+    prob = torch.full((n + 1,), -7.0, device=DEV)
+    data_idx, tree_idx = (torch.full((n + 1,), -7, dtype=torch.int64, device=DEV) for _ in range(2))
+    failed = torch.zeros(1, dtype=torch.int32, device=DEV)
+    L.check(lib.irbpp_sumtree_sample(_ptr(trees), _ptr(index), n, KA_CAP, 1, KA_STEP, seed, KA_TRIES, _ptr(prob), _ptr(data_idx),
+                                     _ptr(tree_idx), _ptr(failed), _stream()), "irbpp_sumtree_sample")
+    torch.cuda.synchronize()
+    assert int(failed.item()) == 0
+    np.testing.assert_array_equal(tree_idx.cpu().numpy()[:n], [t for t, _, _ in want])
+    np.testing.assert_array_equal(data_idx.cpu().numpy()[:n], [t - (KA_CAP - 1) for t, _, _ in want])
+    np.testing.assert_array_equal(prob.cpu().numpy()[:n], np.array([p for _, p, _ in want], dtype=f32))
+    assert prob[n] == -7.0 and data_idx[n] == -7 and tree_idx[n] == -7
+
+
+def test_pooled_sample_draws_the_generators_leaf():
+    """The same for irbpp_replay_pool_sample with values NULL, one memory and one draw: the env field of the counter is
+    0xFFFFFFFF whatever the env.  The write index sits on the first attempt's leaf."""
+    import ctypes
+    from irbpp_amd import replay
+    L, _ = _lib()
+    seed = 0x8000000000000000 | 77
+    tree = _known_answer_tree()
+    w = int(_oracle_tree(tree, KA_CAP).find(f32(uniform01(seed, POOL_RNG_ENV, 0, 0) * tree[0]))[1])
+    t, p, attempts = _known_answer_walk(tree, POOL_RNG_ENV, seed, w)
+    assert attempts > 1
+    assert t != _known_answer_walk(tree, 0, seed, w)[0]                   # (env field 0 would give another leaf)
+    mem = VectorReplayMemory(1, KA_CAP, 1, multi_step=KA_STEP, device=DEV, use_hip=True)
+    mem.sum_tree.copy_(_dev(tree[None, :]))
+    mem.index.fill_(w)
+    mem.full.fill_(True)
+    out = [torch.full((2,), -7, dtype=dt, device=DEV) for dt in (torch.int64, torch.float32, torch.int64, torch.int64, torch.float32)]
+    failed = torch.zeros(1, dtype=torch.int32, device=DEV)
+    view = mem._view()
+    L.check(mem._pool_lib.irbpp_replay_pool_sample(ctypes.byref(view), 1, replay._p(None), seed, KA_TRIES, 0.4,
+                                                   *[replay._p(x) for x in out], replay._p(failed), replay._stream(mem.device)),
+            "irbpp_replay_pool_sample")
+    torch.cuda.synchronize()
+    got = [x.cpu().numpy() for x in out]
+    assert int(failed.item()) == 0
+    assert (got[0][0], got[1][0], got[2][0], got[3][0]) == (0, p, t - (KA_CAP - 1), t)
+    assert got[4][0] == 1.0 and all(g[1] == -7 for g in got)
