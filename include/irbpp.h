@@ -683,6 +683,38 @@ int irbpp_streams_act(const irbpp_stream_weights* w, const float* xg_dev, int64_
                       int32_t s_rows, int32_t n_env, int64_t* action_dev /* may be NULL when only logits are wanted */,
                       float* q_out_dev, int64_t q_stride, float* v_out_dev, float* a_out_dev, void* stream);
 
+/* The shape encoder (model.py: shapeEncoder = Linear(3, hidden) LeakyReLU Linear(hidden, feat) LeakyReLU), float32 on the
+ * device, row-major and contiguous: w1 [hidden][3], b1 [hidden], w2 [feat][hidden], b2 [feat]; slope is the LeakyReLU's
+ * negative_slope (0.01 in the reference), >= 0. */
+typedef struct { const float *w1, *b1, *w2, *b2; int32_t hidden, feat; float slope; } irbpp_shape_encoder;
+/* replaces: the shape branch of DQNBPP.forward without a gradient (model.py:328-335, :365-372): shapeArray[ids.cpu()] on the
+ * host, the gather of the sampled points, the copy to the device, shapeEncoder per row and the max over the points.  Two
+ * launches on `stream`, no atomics: the feature is computed once per shape that occurs in the ids, then gathered.
+ * points_dev float32 [n_shapes][n_points][3], contiguous; indices_dev int32 [k], one index set for all rows, duplicates are
+ * legal; ids_dev [m_rows], element m at ids_dev[m * ids_stride] (a stride in elements: the id column of an [N][obs_len]
+ * observation block passes as it is): float32 when ids_are_float != 0, truncated toward zero as .long() does, else int64;
+ * out_dev float32 [m_rows][feat], rows out_stride floats apart; partial_dev float32 [n_shapes][partial_chunks][feat], a
+ * workspace (rows of shapes that do not occur in the ids are neither written nor read).
+ * The float32 arithmetic is defined (csrc/irbpp_shapefeat.hip): for row m with u = ids[m] and p_j = points[u][indices[j]],
+ *   h1_j[i] = leaky(fmaf(p_j[2], w1[i][2], fmaf(p_j[1], w1[i][1], fmaf(p_j[0], w1[i][0], b1[i])))),
+ *   s_j[f]  = b2[f], then s_j[f] = fmaf(h1_j[i], w2[f][i], s_j[f]) for i ascending,  leaky(s) = s > 0 ? s : slope * s,
+ *   out[m][f] = max_j leaky(s_j[f]),
+ * single-rounding fused multiply-adds, never split or re-associated.  The max is sticky for NaN (any NaN term gives the quiet
+ * NaN 0x7fc00000, as torch.max does; fmaxf would drop it) and puts +0 above -0; it is exact, so the result does not depend
+ * on partial_chunks, m_rows or the strides.  An id outside [0, n_shapes) -- NaN and infinite float ids included -- gives a NaN
+ * row (torch's indexing raises there); an index outside [0, n_points) counts as a NaN point, so every row comes out NaN.
+ * Nothing out of range is read in either case.
+ * IRBPP_ERR_ARG unless 1 <= hidden, feat <= 256, slope >= 0, 1 <= k <= 4096, 1 <= n_shapes <= 65535, n_points >= 1,
+ * m_rows >= 1, ids_stride >= 1, out_stride >= feat, partial_chunks == irbpp_shape_features_chunks(n_shapes, k) and no
+ * pointer is NULL. */
+int irbpp_shape_features(const float* points_dev, int32_t n_shapes, int32_t n_points, const int32_t* indices_dev, int32_t k,
+                         const void* ids_dev, int32_t ids_are_float, int32_t ids_stride, int32_t m_rows,
+                         const irbpp_shape_encoder* enc, float* partial_dev, int32_t partial_chunks, float* out_dev,
+                         int32_t out_stride, void* stream);
+/* The number of chunks the k points are split into for this many shapes (small shape sets get more chunks, so that they
+ * still fill the chip): what partial_dev must be sized by.  0 outside the limits above. */
+int irbpp_shape_features_chunks(int32_t n_shapes, int32_t k);
+
 /* Tooling: when cycles_dev != NULL every later transition launch stores, per bin, one row
  * int64[num_bins][16]: shader-clock stamps 0 start, 1 action applied, 2 overlap test done,
  * 3 contour stage done, 4 observation written; 5..7 contour-stage detail; 8/9 the 100 MHz wall

@@ -27,6 +27,7 @@
 #include "irbpp_dueling.hip"        // the same from the network's logits: dueling combine + softmax fused in (irbpp_dueling_act, irbpp_dueling_target)
 #include "irbpp_dueling_loss.hip"   // the loss that carries the gradient, forward and backward from the logits (irbpp_dueling_loss, irbpp_dueling_loss_backward)
 #include "irbpp_streams.hip"        // the four noisy layers of the value and advantage streams in front of the dueling head (irbpp_noisy_weights, irbpp_streams_act)
+#include "irbpp_shapefeat.hip"      // the shape branch in front of the network: sampled points to shape features (irbpp_shape_features)
 #include "irbpp_metrics.hip"        // the trainer's episode metrics (irbpp_set_episode_window)
 #include "irbpp_itemgen.h"
 #include "irbpp_plan.h"             // which kernels a transition launches: the registry of kernels and plan_transition
@@ -1252,6 +1253,34 @@ int irbpp_streams_act(const irbpp_stream_weights* w, const float* xg_dev, int64_
     if (!dueling_lds((const void*)irbpp_streams_finish_kernel, w->atoms, s_rows, &lds)) return IRBPP_ERR_HIP;
     hipLaunchKernelGGL(irbpp_streams_finish_kernel, dim3(n_env), dim3(DUELING_THREADS), lds, (hipStream_t)stream, w->w_hv, w->b_hv,
                        w->w_zv, w->b_zv, xg_dev, (const float*)a_out_dev, support_dev, obs_dev, action_dev, q_out_dev, g);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+int irbpp_shape_features_chunks(int32_t n_shapes, int32_t k) {
+    if (n_shapes < 1 || n_shapes > SHAPE_MAX_SHAPES || k < 1 || k > SHAPE_MAX_POINTS) return 0;
+    return shape_chunks(n_shapes, k);
+}
+
+int irbpp_shape_features(const float* points_dev, int32_t n_shapes, int32_t n_points, const int32_t* indices_dev, int32_t k,
+                         const void* ids_dev, int32_t ids_are_float, int32_t ids_stride, int32_t m_rows,
+                         const irbpp_shape_encoder* enc, float* partial_dev, int32_t partial_chunks, float* out_dev,
+                         int32_t out_stride, void* stream) {
+    if (!points_dev || !indices_dev || !ids_dev || !enc || !enc->w1 || !enc->b1 || !enc->w2 || !enc->b2 || !partial_dev ||
+        !out_dev || enc->hidden < 1 || enc->hidden > SHAPE_MAX_WIDTH || enc->feat < 1 || enc->feat > SHAPE_MAX_WIDTH ||
+        !(enc->slope >= 0.0f) || k < 1 || k > SHAPE_MAX_POINTS || n_shapes < 1 || n_shapes > SHAPE_MAX_SHAPES || n_points < 1 ||
+        m_rows < 1 || ids_stride < 1 || out_stride < enc->feat || partial_chunks != shape_chunks(n_shapes, k))
+        return IRBPP_ERR_ARG;
+    ShapeArgs g;
+    g.ids_stride = ids_stride, g.m_rows = m_rows, g.out_stride = out_stride;
+    g.n_shapes = n_shapes, g.n_points = n_points, g.k = k, g.ids_are_float = ids_are_float != 0, g.hidden = enc->hidden;
+    g.feat = enc->feat, g.chunk_points = shape_chunk_points(n_shapes, k), g.chunks = partial_chunks, g.slope = enc->slope;
+    const int threads = shape_threads(enc->feat);
+    hipLaunchKernelGGL(irbpp_shape_partial_kernel, dim3(n_shapes, partial_chunks), dim3(threads), 0, (hipStream_t)stream, points_dev,
+                       indices_dev, ids_dev, enc->w1, enc->b1, enc->w2, enc->b2, partial_dev, g);
+    if (hipGetLastError() != hipSuccess) return IRBPP_ERR_HIP;
+    const long long elems = (long long)m_rows * enc->feat;
+    hipLaunchKernelGGL(irbpp_shape_gather_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)partial_dev, ids_dev, out_dev, g);
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
 }
 

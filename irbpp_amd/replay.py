@@ -1021,6 +1021,190 @@ def streams_logits(x: torch.Tensor, x_global: torch.Tensor, weights: StreamWeigh
     return _streams_logits_cpu(x, xg, weights)
 
 
+# The same question for the shape branch in front of the network ("The shape branch"): the
+# de-duplicated torch formulation or the two launches of irbpp_shape_features.  The kernels: tools/shape_feature_rates.py
+# measured them on an MI355X at 0.073 ms against 0.446 ms for torch's layers on the unique ids at 4096 rows of 8 shapes, 0.189
+# against 0.515 ms with 100 shapes, and 0.061 / 0.164 against 0.323 / 0.373 ms at 1024 rows: beyond the larger spread at every
+# acting size (profiles/shape_features/).  use_hip=False asks for torch's layers.
+SHAPE_FEATURES_HIP_DEFAULT = True
+
+SHAPE_MAX_WIDTH, SHAPE_MAX_POINTS, SHAPE_MAX_SHAPES = 256, 4096, 65535
+
+
+class _IrbppShapeEncoder(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2")] + [("hidden", C.c_int32), ("feat", C.c_int32), ("slope", C.c_float)]
+
+
+class ShapePoints(object):
+    """The reference's ``args.shapeArray`` (float [n_shapes, P, 3], numpy or a tensor: P surface points per shape) as one float32
+    table on ``device``, uploaded once: the shape branch then never leaves the device (model.py:328-335 indexes the CPU array
+    with ``next_item_ID.cpu()`` and copies the gathered points back on every forward).  ``updateShapeArray``'s periodic
+    re-subsampling is the caller's business: build a new ShapePoints."""
+
+    def __init__(self, shape_array, device):
+        t = torch.as_tensor(shape_array)
+        if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError("shape_array must be [n_shapes, P, 3]")
+        self.points = t.detach().to(device=device, dtype=torch.float32).contiguous()
+        self.device = self.points.device
+        self.n_shapes, self.n_points = int(t.shape[0]), int(t.shape[1])
+        self._workspace = {}
+
+    def draw_indices(self, k: int, generator=None) -> torch.Tensor:
+        """int32 [k] on the device, uniform in [0, P) with replacement: the role of model.py's ``np.random.randint`` (not its
+        global stream: a caller who needs the reference's draws passes its own indices)."""
+        return torch.randint(0, self.n_points, (int(k),), device=self.device, generator=generator, dtype=torch.int32)
+
+    def gather(self, ids: torch.Tensor, indices: torch.Tensor) -> torch.Tensor:
+        """``shapeArray[ids][:, indices]`` -> float32 [M, k, 3] by torch indexing on the device: what the forward that carries
+        a gradient feeds to ``self.shapeEncoder``."""
+        ids = ids.reshape(-1).to(device=self.device, dtype=torch.long)
+        return self.points[ids[:, None], indices.to(device=self.device, dtype=torch.long)[None, :]]
+
+    def _partial(self, chunks: int, feat: int) -> torch.Tensor:
+        key = (chunks, feat)
+        if key not in self._workspace:
+            self._workspace[key] = torch.empty((self.n_shapes, chunks, feat), dtype=torch.float32, device=self.device)
+        return self._workspace[key]
+
+
+class ShapeEncoderWeights(object):
+    """``shapeEncoder``'s two Linear layers as float32 contiguous tensors (w1 [H1, 3], b1 [H1], w2 [F, H1], b2 [F]) and the
+    LeakyReLU's slope: what shape_features multiplies by.  Copies: call ``refresh()`` after every optimiser step."""
+
+    def __init__(self, linear1, linear2, negative_slope: float = 0.01):
+        self.layers = (linear1, linear2)
+        self.slope = float(negative_slope)
+        self.hidden, three = (int(d) for d in linear1.weight.shape)
+        self.feat = int(linear2.weight.shape[0])
+        if three != 3 or tuple(linear2.weight.shape) != (self.feat, self.hidden) or tuple(linear1.bias.shape) != (self.hidden,) or \
+                tuple(linear2.bias.shape) != (self.feat,):
+            raise ValueError("shape encoder: Linear(3, H1) and Linear(H1, F) with biases")
+        if not (1 <= self.hidden <= SHAPE_MAX_WIDTH and 1 <= self.feat <= SHAPE_MAX_WIDTH and self.slope >= 0):
+            raise ValueError("shape encoder: 1 <= H1, F <= 256 and negative_slope >= 0")
+        self.device = linear1.weight.device
+        self.refresh()
+
+    @classmethod
+    def from_layers(cls, linear1, linear2, negative_slope: float = 0.01) -> "ShapeEncoderWeights":
+        return cls(linear1, linear2, negative_slope)
+
+    @torch.no_grad()
+    def refresh(self) -> "ShapeEncoderWeights":
+        l1, l2 = self.layers
+        self.w1, self.b1, self.w2, self.b2 = (_f32(t.detach(), self.device).clone() for t in (l1.weight, l1.bias, l2.weight, l2.bias))
+        return self
+
+    def _struct(self) -> _IrbppShapeEncoder:
+        return _IrbppShapeEncoder(self.w1.data_ptr(), self.b1.data_ptr(), self.w2.data_ptr(), self.b2.data_ptr(), self.hidden,
+                                  self.feat, self.slope)
+
+
+def _max_sticky_np(h):
+    """max over axis 0 of a float32 array as the kernels take it: on keys (the bits mapped to uint32 in the floats' order, -0
+    below +0, every NaN on top), so any NaN gives the quiet NaN 0x7fc00000."""
+    import numpy as np
+    b = np.ascontiguousarray(h, dtype=np.float32).view(np.uint32)
+    key = np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000))
+    key = np.where((b & np.uint32(0x7fffffff)) > np.uint32(0x7f800000), np.uint32(0xffffffff), key).max(axis=0)
+    bits = np.where(key & np.uint32(0x80000000), key & np.uint32(0x7fffffff), ~key)
+    return np.where(key == np.uint32(0xffffffff), np.uint32(0x7fc00000), bits).astype(np.uint32).view(np.float32)
+
+
+def _shape_ids(ids: torch.Tensor, n_shapes: int) -> torch.Tensor:
+    """ids (float: truncated toward zero like .long(); NaN and infinities are bad) -> int64 with -1 for every bad id."""
+    if ids.is_floating_point():
+        v = ids.to(torch.float32)
+        ok = (v > -1) & (v < n_shapes)
+        return torch.where(ok, torch.where(ok, v, torch.zeros_like(v)).long(), torch.full_like(v, -1, dtype=torch.long))
+    v = ids.long()
+    return torch.where((v >= 0) & (v < n_shapes), v, torch.full_like(v, -1))
+
+
+def _shape_features_cpu(ids: torch.Tensor, points: ShapePoints, indices: torch.Tensor, w: ShapeEncoderWeights) -> torch.Tensor:
+    import numpy as np
+    f32 = np.float32
+    n = lambda t: t.detach().to(torch.float32).cpu().numpy()  # noqa: E731
+    leaky = lambda s: np.where(s > 0, s, f32(w.slope) * s).astype(f32)  # noqa: E731
+    u = _shape_ids(ids, points.n_shapes).numpy()
+    idx = indices.detach().cpu().numpy().astype(np.int64)
+    bad = (idx < 0) | (idx >= points.n_points)
+    out = np.full((u.shape[0], w.feat), np.nan, dtype=f32)
+    table = n(points.points)
+    with np.errstate(all="ignore"):
+        for s in np.unique(u[u >= 0]):
+            p = table[s][np.where(bad, 0, idx)].copy()
+            p[bad] = np.nan
+            h2 = leaky(_lin_np(n(w.w2), n(w.b2), leaky(_lin_np(n(w.w1), n(w.b1), p))))
+            out[u == s] = _max_sticky_np(h2)
+    return torch.from_numpy(out)
+
+
+def _shape_features_torch(ids, points: ShapePoints, indices, w: ShapeEncoderWeights) -> torch.Tensor:
+    F = torch.nn.functional
+    u = _shape_ids(ids, points.n_shapes)
+    idx = indices.long()
+    bad_idx = ((idx < 0) | (idx >= points.n_points)).any()
+    uniq, inv = torch.unique(u.clamp(min=0), return_inverse=True)
+    p = points.points[uniq[:, None], idx.clamp(0, points.n_points - 1)[None, :]]
+    h = F.leaky_relu(F.linear(F.leaky_relu(F.linear(p, w.w1, w.b1), w.slope), w.w2, w.b2), w.slope)
+    feat = torch.max(h, dim=1)[0][inv]
+    return torch.where((u < 0)[:, None] | bad_idx, torch.full_like(feat, float("nan")), feat)
+
+
+@torch.no_grad()
+def shape_features(ids: torch.Tensor, points: ShapePoints, indices: torch.Tensor, weights: ShapeEncoderWeights, *,
+                   use_hip: Optional[bool] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The shape branch of DQNBPP.forward without a gradient (model.py:328-335, :365-372): the observation's item ids ->
+    ``shape_feature`` float32 [M, F], on ``points``' device.  ``ids``: any shape (flattened: [B, K] gives [B*K, F]), integers or
+    the observation's float32 column itself (truncated toward zero like ``.long()``), strided columns as they are;
+    ``indices``: the forward's one index set, int [k] (``points.draw_indices``); ``out``: a float32 [M, F] tensor with
+    contiguous rows (a slice of a wider tensor passes) to write into.  Defined arithmetic (csrc/irbpp_shapefeat.hip: fmaf chains
+    from the bias, a max with a sticky NaN); an id outside [0, n_shapes) gives a NaN row, an index outside [0, P) makes every
+    row NaN.  The feature is computed once per distinct id in every form: on CPU tensors the exact numpy emulation of the
+    definition, on a HIP device with ``use_hip=True`` (``None`` takes SHAPE_FEATURES_HIP_DEFAULT) the two launches of
+    irbpp_shape_features, else torch's layers on the unique ids (rocBLAS's summation order: close to, not bit-equal with, the
+    definition)."""
+    dev = points.device
+    ids = ids.detach()
+    if ids.device != dev:
+        ids = ids.to(dev)
+    if ids.is_floating_point():
+        ids = ids if ids.dtype == torch.float32 else ids.to(torch.float32)
+    elif ids.dtype != torch.int64:
+        ids = ids.long()
+    ids = ids.reshape(-1)                                # a view where the strides allow it (a column of the observation)
+    indices = indices.detach().to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    M, k, F_ = int(ids.shape[0]), int(indices.shape[0]), weights.feat
+    if not (1 <= k <= SHAPE_MAX_POINTS) or M < 1 or points.n_shapes > SHAPE_MAX_SHAPES:
+        raise ValueError("shape_features: indices int [k] with 1 <= k <= 4096, at least one id, at most 65535 shapes")
+    if weights.device != dev:
+        raise ValueError("shape_features: the weights and the points live on different devices")
+    if out is not None and (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (M, F_) or
+                            (F_ > 1 and out.stride(1) != 1) or out.stride(0) < F_):
+        raise ValueError(f"out must be a float32 [{M}, {F_}] tensor on the points' device with contiguous rows")
+    lib = _head_lib(points.points, use_hip, SHAPE_FEATURES_HIP_DEFAULT)
+    if lib is None:
+        res = _shape_features_torch(ids, points, indices, weights) if dev.type == "cuda" else \
+            _shape_features_cpu(ids, points, indices, weights)
+        if out is None:
+            return res
+        out.copy_(res)
+        return out
+    from . import _lib
+    if out is None:
+        out = torch.empty((M, F_), dtype=torch.float32, device=dev)
+    if M > 1 and ids.stride(0) < 1:
+        ids = ids.contiguous()
+    chunks = lib.irbpp_shape_features_chunks(points.n_shapes, k)
+    enc = weights._struct()
+    _lib.check(lib.irbpp_shape_features(_p(points.points), points.n_shapes, points.n_points, _p(indices), k, _p(ids),
+                                        1 if ids.is_floating_point() else 0, max(int(ids.stride(0)), 1), M, C.byref(enc),
+                                        _p(points._partial(chunks, F_)), chunks, _p(out), max(int(out.stride(0)), F_),
+                                        _stream(dev)), "irbpp_shape_features")
+    return out
+
+
 def actor_step(envs, policy, memory: VectorReplayMemory, state: torch.Tensor, reward_clip: float = 0.0):
     """One iteration of the trainer's acting loop (trainer.py:160-186) without per-env Python:
     mask -> policy -> envs.step -> clip -> append.  ``envs`` is a GpuPackingEnv (device-tensor
