@@ -715,6 +715,41 @@ int irbpp_shape_features(const float* points_dev, int32_t n_shapes, int32_t n_po
  * still fill the chip): what partial_dev must be sized by.  0 outside the limits above. */
 int irbpp_shape_features_chunks(int32_t n_shapes, int32_t k);
 
+/* The layers of the embedding stage (model.py: heightEncoder = Conv2d(1, c1, 4, 2, 1) LeakyReLU Conv2d(c1, c2, 4, 2, 1) LeakyReLU
+ * Conv2d(c2, c3, 3, 1, 1) LeakyReLU; init_candidate_embed = Linear(4, cand_hidden) LeakyReLU Linear(cand_hidden, cand_embed);
+ * project_layer = Linear(feat + c3 (map_len/4)^2 + cand_embed, proj_hidden) LeakyReLU Linear(proj_hidden, embed)), float32 on
+ * the device, contiguous, in torch's layouts: convolution weights [out][in][ky][kx], linear weights [out][in].  map_len is the
+ * heightmap's side L; slope the LeakyReLUs' negative_slope (0.01 in the reference), >= 0. */
+typedef struct { const float *w_conv1, *b_conv1, *w_conv2, *b_conv2, *w_conv3, *b_conv3, *w_c1, *b_c1, *w_c2, *b_c2, *w_p1, *b_p1,
+                 *w_p2, *b_p2;
+                 int32_t map_len, c1, c2, c3, feat, cand_hidden, cand_embed, proj_hidden, embed; float slope; } irbpp_embed_weights;
+/* replaces: the embedding stage of DQNBPP.forward without a gradient (model.py:318-326, :337-352, bufferSize == 1): the
+ * heightmap CNN, init_candidate_embed per candidate row, the [n_env * s_rows][feat + M + cand_embed] concatenation, both layers
+ * of project_layer, the boolean-mask zeroing of the invalid rows and the mean over the rows.  Two launches on `stream`, no
+ * atomics: the part of every project_layer[0] chain that is the same for all rows of a bin (shape feature, map feature) runs
+ * once per bin into base_dev, every row continues from there; neither the concatenation nor the hidden blocks reach memory.
+ * obs_dev float32 [n_env][obs_stride]: obs[5r .. 5r+3] candidate r, obs[5r+4] its mask, obs[5 s_rows + 9 ..] the map_len x
+ * map_len heightmap, row-major (the item id at obs[5 s_rows] is not read); shape_feat_dev float32 [n_env][feat], rows
+ * feat_stride floats apart (irbpp_shape_features' out); base_dev float32 [n_env][proj_hidden], a workspace; x_dev float32
+ * [n_env][s_rows][embed], row r of env e at x_dev + e*env_stride + r*row_stride; xg_dev float32 [n_env][embed], rows
+ * xg_stride floats apart: what irbpp_streams_act takes as x_dev and xg_dev.
+ * The float32 arithmetic is defined (csrc/irbpp_embed.hip): every output of a layer is one chain acc = b[j]; acc =
+ * fmaf(x[k], W[j][k], acc) for k ascending, a single-rounding fused multiply-add, never split or re-associated; a
+ * convolution's chain runs over its taps in ascending (c_in, ky, kx), a tap in the padding taking part with the input +0.0;
+ * project_layer[0]'s chain runs over the shape feature, the map feature and the candidate embedding in that order, as over
+ * the concatenation; leaky(s) = s > 0 ? s : slope * s.  A row is valid iff its mask == 1.0f exactly (a NaN mask is invalid);
+ * an invalid row is +0.0 in every element of x, whatever its candidate holds.  xg is the mean over all s_rows rows of x in
+ * irbpp_dueling_act's summation: 16 interleaved partial sums (part g: rows g, g+16, .. ascending from 0.0) added left to
+ * right, divided by (float)s_rows.  Reproducible bit for bit whatever n_env and the strides; no index depends on data, so
+ * nothing is accessed out of range whatever the values.
+ * IRBPP_ERR_ARG unless map_len is a multiple of 4 in [8, 32], 1 <= c1 <= 16, 1 <= c2 <= 32, 1 <= c3 <= 4, 1 <= feat,
+ * cand_embed, proj_hidden, embed <= 256, 1 <= cand_hidden <= 64, slope >= 0, 1 <= s_rows <= 1024, n_env >= 1,
+ * obs_stride >= 5*s_rows + 9 + map_len^2, feat_stride >= feat, row_stride >= embed, env_stride >= (s_rows-1)*row_stride +
+ * embed, xg_stride >= embed and no pointer is NULL. */
+int irbpp_embed(const irbpp_embed_weights* w, const float* obs_dev, int64_t obs_stride, const float* shape_feat_dev,
+                int64_t feat_stride, int32_t s_rows, int32_t n_env, float* base_dev /* workspace [n_env][proj_hidden] */,
+                float* x_dev, int64_t env_stride, int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream);
+
 /* Tooling: when cycles_dev != NULL every later transition launch stores, per bin, one row
  * int64[num_bins][16]: shader-clock stamps 0 start, 1 action applied, 2 overlap test done,
  * 3 contour stage done, 4 observation written; 5..7 contour-stage detail; 8/9 the 100 MHz wall

@@ -28,6 +28,7 @@
 #include "irbpp_dueling_loss.hip"   // the loss that carries the gradient, forward and backward from the logits (irbpp_dueling_loss, irbpp_dueling_loss_backward)
 #include "irbpp_streams.hip"        // the four noisy layers of the value and advantage streams in front of the dueling head (irbpp_noisy_weights, irbpp_streams_act)
 #include "irbpp_shapefeat.hip"      // the shape branch in front of the network: sampled points to shape features (irbpp_shape_features)
+#include "irbpp_embed.hip"          // the embedding stage: heightmap CNN, candidate rows, masked mean (irbpp_embed)
 #include "irbpp_metrics.hip"        // the trainer's episode metrics (irbpp_set_episode_window)
 #include "irbpp_itemgen.h"
 #include "irbpp_plan.h"             // which kernels a transition launches: the registry of kernels and plan_transition
@@ -1281,6 +1282,35 @@ int irbpp_shape_features(const float* points_dev, int32_t n_shapes, int32_t n_po
     const long long elems = (long long)m_rows * enc->feat;
     hipLaunchKernelGGL(irbpp_shape_gather_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const float*)partial_dev, ids_dev, out_dev, g);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+int irbpp_embed(const irbpp_embed_weights* w, const float* obs_dev, int64_t obs_stride, const float* shape_feat_dev,
+                int64_t feat_stride, int32_t s_rows, int32_t n_env, float* base_dev, float* x_dev, int64_t env_stride,
+                int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream) {
+    if (!w || !w->w_conv1 || !w->b_conv1 || !w->w_conv2 || !w->b_conv2 || !w->w_conv3 || !w->b_conv3 || !w->w_c1 || !w->b_c1 ||
+        !w->w_c2 || !w->b_c2 || !w->w_p1 || !w->b_p1 || !w->w_p2 || !w->b_p2 || !obs_dev || !shape_feat_dev || !base_dev ||
+        !x_dev || !xg_dev || w->map_len < 8 || w->map_len > EMBED_MAX_MAP || w->map_len % 4 != 0 || w->c1 < 1 ||
+        w->c1 > EMBED_MAX_C1 || w->c2 < 1 || w->c2 > EMBED_MAX_C2 || w->c3 < 1 || w->c3 > EMBED_MAX_C3 || w->feat < 1 ||
+        w->feat > EMBED_MAX_WIDTH || w->cand_embed < 1 || w->cand_embed > EMBED_MAX_WIDTH || w->proj_hidden < 1 ||
+        w->proj_hidden > EMBED_MAX_WIDTH || w->embed < 1 || w->embed > EMBED_MAX_WIDTH || w->cand_hidden < 1 ||
+        w->cand_hidden > EMBED_MAX_CAND_HIDDEN || !(w->slope >= 0.0f) || s_rows < 1 || s_rows > HEAD_MAX_ROWS || n_env < 1 ||
+        obs_stride < (int64_t)5 * s_rows + 9 + (int64_t)w->map_len * w->map_len || feat_stride < w->feat || row_stride < w->embed ||
+        env_stride < (int64_t)(s_rows - 1) * row_stride + w->embed || xg_stride < w->embed)
+        return IRBPP_ERR_ARG;
+    EmbedArgs g;
+    g.obs_stride = obs_stride, g.feat_stride = feat_stride, g.env_stride = env_stride, g.row_stride = row_stride, g.xg_stride = xg_stride;
+    g.map_len = w->map_len, g.c1 = w->c1, g.c2 = w->c2, g.c3 = w->c3, g.feat = w->feat, g.cand_hidden = w->cand_hidden;
+    g.cand_embed = w->cand_embed, g.proj_hidden = w->proj_hidden, g.embed = w->embed, g.s_rows = s_rows, g.slope = w->slope;
+    hipLaunchKernelGGL(irbpp_embed_bin_kernel, dim3(n_env), dim3(EMBED_BIN_THREADS), 0, (hipStream_t)stream, w->w_conv1, w->b_conv1,
+                       w->w_conv2, w->b_conv2, w->w_conv3, w->b_conv3, w->w_p1, w->b_p1, obs_dev, shape_feat_dev, base_dev, g);
+    if (hipGetLastError() != hipSuccess) return IRBPP_ERR_HIP;
+    const size_t lds = (size_t)embed_rows_lds_floats(w->cand_hidden, w->cand_embed, w->proj_hidden, w->embed) * sizeof(float);
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)irbpp_embed_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)lds) != hipSuccess)
+        return IRBPP_ERR_HIP;
+    hipLaunchKernelGGL(irbpp_embed_rows_kernel, dim3(n_env), dim3(EMBED_ROW_THREADS), lds, (hipStream_t)stream, w->w_c1, w->b_c1,
+                       w->w_c2, w->b_c2, w->w_p1, w->w_p2, w->b_p2, obs_dev, (const float*)base_dev, x_dev, xg_dev, g);
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
 }
 

@@ -1205,6 +1205,245 @@ def shape_features(ids: torch.Tensor, points: ShapePoints, indices: torch.Tensor
     return out
 
 
+# The same question for the embedding stage between the two ("The embedding stage"): torch's layers in
+# the factored form (MIOpen's convolutions, rocBLAS for the project layers) or the two launches of irbpp_embed.  Torch's
+# layers, since tools/embed_rates.py measured them on an MI355X at 5.38 ms against 11.14 ms for the kernels at 4096 bins x 500
+# candidates and 1.43 against 2.84 ms at 1024 (profiles/embed/): the matrix units win over the defined fmaf chain, as for the
+# streams.  use_hip=True asks for the kernels (the reproducible forward).
+EMBED_HIP_DEFAULT = False
+
+EMBED_MAX_WIDTH, EMBED_MAX_CAND_HIDDEN, EMBED_MAX_ROWS = 256, 64, 1024
+_EMBED_FIELDS = ("w_conv1", "b_conv1", "w_conv2", "b_conv2", "w_conv3", "b_conv3", "w_c1", "b_c1", "w_c2", "b_c2", "w_p1", "b_p1",
+                 "w_p2", "b_p2")
+_EMBED_SIZES = ("map_len", "c1", "c2", "c3", "feat", "cand_hidden", "cand_embed", "proj_hidden", "embed")
+
+
+class _IrbppEmbedWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in _EMBED_FIELDS] + [(n, C.c_int32) for n in _EMBED_SIZES] + [("slope", C.c_float)]
+
+
+class EmbedWeights(object):
+    """The layers of DQNBPP's embedding stage as float32 contiguous tensors in torch's layouts: ``heightEncoder``'s three
+    Conv2d (4x4 stride 2 pad 1, 4x4 stride 2 pad 1, 3x3 stride 1 pad 1), ``init_candidate_embed``'s two Linear and
+    ``project_layer``'s two Linear, and the LeakyReLUs' slope: what embed multiplies by.  Takes the three ``nn.Sequential``s
+    (any iterables whose Conv2d / Linear members come in order; the activations between them are skipped) and checks that the
+    shapes fit each other; ``map_len`` is the heightmap's side L (the reference asserts 32), from which the shape feature's
+    width follows: F = project_layer[0].in_features - c3 (L/4)^2 - cand_embed.  Copies: call ``refresh()`` after every
+    optimiser step."""
+
+    def __init__(self, height_encoder, init_candidate_embed, project_layer, negative_slope: float = 0.01, *, map_len: int = 32):
+        convs = [m for m in height_encoder if getattr(m, "weight", None) is not None and m.weight.dim() == 4]
+        cands = [m for m in init_candidate_embed if getattr(m, "weight", None) is not None and m.weight.dim() == 2]
+        projs = [m for m in project_layer if getattr(m, "weight", None) is not None and m.weight.dim() == 2]
+        if len(convs) != 3 or len(cands) != 2 or len(projs) != 2:
+            raise ValueError("embed: three Conv2d, two Linear (candidates) and two Linear (project layer)")
+        self.layers = tuple(convs + cands + projs)
+        if any(m.bias is None for m in self.layers):
+            raise ValueError("embed: every layer has a bias")
+        self.slope, self.map_len = float(negative_slope), int(map_len)
+        for m, (k, s, p) in zip(convs, ((4, 2, 1), (4, 2, 1), (3, 1, 1))):
+            if tuple(m.weight.shape[2:]) != (k, k) or tuple(getattr(m, "stride", (s, s))) != (s, s) or \
+                    tuple(getattr(m, "padding", (p, p))) != (p, p):
+                raise ValueError("embed: Conv2d(1, c1, 4, 2, 1), Conv2d(c1, c2, 4, 2, 1), Conv2d(c2, c3, 3, 1, 1)")
+        self.c1, self.c2, self.c3 = (int(m.weight.shape[0]) for m in convs)
+        self.cand_hidden, self.cand_embed = int(cands[0].weight.shape[0]), int(cands[1].weight.shape[0])
+        self.proj_hidden, self.embed = int(projs[0].weight.shape[0]), int(projs[1].weight.shape[0])
+        if self.map_len % 4 != 0 or not 8 <= self.map_len <= 32:
+            raise ValueError("embed: map_len is a multiple of 4 in [8, 32]")
+        self.map_feat = self.c3 * (self.map_len // 4) ** 2
+        self.feat = int(projs[0].weight.shape[1]) - self.map_feat - self.cand_embed
+        want = [(self.c1, 1, 4, 4), (self.c2, self.c1, 4, 4), (self.c3, self.c2, 3, 3), (self.cand_hidden, 4),
+                (self.cand_embed, self.cand_hidden), (self.proj_hidden, self.feat + self.map_feat + self.cand_embed),
+                (self.embed, self.proj_hidden)]
+        for m, shape in zip(self.layers, want):
+            if tuple(m.weight.shape) != shape or tuple(m.bias.shape) != shape[:1]:
+                raise ValueError(f"embed: a weight of shape {tuple(m.weight.shape)} beside the expected {shape}")
+        if not (1 <= self.c1 <= 16 and 1 <= self.c2 <= 32 and 1 <= self.c3 <= 4 and 1 <= self.cand_hidden <= EMBED_MAX_CAND_HIDDEN and
+                all(1 <= v <= EMBED_MAX_WIDTH for v in (self.feat, self.cand_embed, self.proj_hidden, self.embed)) and self.slope >= 0):
+            raise ValueError("embed: 1 <= c1 <= 16, 1 <= c2 <= 32, 1 <= c3 <= 4, 1 <= cand_hidden <= 64, 1 <= feat, cand_embed, "
+                             "proj_hidden, embed <= 256 and negative_slope >= 0")
+        self.device = convs[0].weight.device
+        self._workspace = {}
+        self.refresh()
+
+    @classmethod
+    def from_layers(cls, height_encoder, init_candidate_embed, project_layer, negative_slope: float = 0.01, *,
+                    map_len: int = 32) -> "EmbedWeights":
+        return cls(height_encoder, init_candidate_embed, project_layer, negative_slope, map_len=map_len)
+
+    @torch.no_grad()
+    def refresh(self) -> "EmbedWeights":
+        for i, m in enumerate(self.layers):
+            setattr(self, _EMBED_FIELDS[2 * i], _f32(m.weight.detach(), self.device).clone())
+            setattr(self, _EMBED_FIELDS[2 * i + 1], _f32(m.bias.detach(), self.device).clone())
+        return self
+
+    def _struct(self) -> _IrbppEmbedWeights:
+        return _IrbppEmbedWeights(*(getattr(self, n).data_ptr() for n in _EMBED_FIELDS), *(getattr(self, n) for n in _EMBED_SIZES),
+                                  self.slope)
+
+    def _base(self, n_env: int) -> torch.Tensor:
+        if n_env not in self._workspace:
+            self._workspace = {n_env: torch.empty((n_env, self.proj_hidden), dtype=torch.float32, device=self.device)}
+        return self._workspace[n_env]
+
+
+def _chain_np(acc, w, x):
+    """The chains acc [..., J] continued over x [..., K] against w [J, K], k ascending: _lin_np from where another left off."""
+    for k in range(w.shape[1]):
+        acc = _fmaf_np(x[..., k:k + 1], w[:, k], acc)
+    return acc
+
+
+def _conv_np(x, w, b, stride: int, pad: int):
+    """The defined convolution on float32 numpy arrays: x [N, Cin, H, H], w [Cout, Cin, k, k] -> [N, Cout, H', H'], every
+    output _lin_np over its zero-padded patch in (c_in, ky, kx) order."""
+    import numpy as np
+    k = w.shape[2]
+    n_out = (x.shape[2] + 2 * pad - k) // stride + 1
+    xp = np.zeros(x.shape[:2] + (x.shape[2] + 2 * pad, x.shape[3] + 2 * pad), dtype=np.float32)
+    xp[:, :, pad:pad + x.shape[2], pad:pad + x.shape[3]] = x
+    span = stride * (n_out - 1) + 1
+    patches = np.stack([xp[:, ci, ky:ky + span:stride, kx:kx + span:stride] for ci in range(x.shape[1]) for ky in range(k)
+                        for kx in range(k)], axis=-1)
+    return np.ascontiguousarray(np.moveaxis(_lin_np(w.reshape(w.shape[0], -1), b, patches), -1, 1))
+
+
+def _mean_rows_np(x):
+    """dueling_mean over axis 1 of a float32 [N, S, E] array: 16 interleaved parts from 0.0, added left to right, over S."""
+    import numpy as np
+    S = x.shape[1]
+    total = None
+    for g in range(16):
+        s = np.zeros((x.shape[0], x.shape[2]), dtype=np.float32)
+        for i in range(g, S, 16):
+            s = s + x[:, i]
+        total = s if total is None else total + s
+    return total / np.float32(S)
+
+
+def _embed_cpu(state: torch.Tensor, sf: torch.Tensor, w: EmbedWeights, S: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    import numpy as np
+    f32 = np.float32
+    n = lambda t: t.detach().to(torch.float32).cpu().numpy()  # noqa: E731
+    leaky = lambda s: np.where(s > 0, s, f32(w.slope) * s).astype(f32)  # noqa: E731
+    obs, sf = n(state), n(sf)
+    N, L, F_, M = obs.shape[0], w.map_len, w.feat, w.map_feat
+    with np.errstate(all="ignore"):
+        rows = obs[:, :5 * S].reshape(N, S, 5)
+        hm = obs[:, 5 * S + 9:5 * S + 9 + L * L].reshape(N, 1, L, L)
+        a = leaky(_conv_np(hm, n(w.w_conv1), n(w.b_conv1), 2, 1))
+        a = leaky(_conv_np(a, n(w.w_conv2), n(w.b_conv2), 2, 1))
+        fmap = leaky(_conv_np(a, n(w.w_conv3), n(w.b_conv3), 1, 1)).reshape(N, M)
+        w_p1 = n(w.w_p1)
+        base = np.broadcast_to(n(w.b_p1), (N, w.proj_hidden)).astype(f32)
+        base = _chain_np(_chain_np(base, w_p1[:, :F_], sf), w_p1[:, F_:F_ + M], fmap)
+        e2 = _lin_np(n(w.w_c2), n(w.b_c2), leaky(_lin_np(n(w.w_c1), n(w.b_c1), rows[:, :, :4])))
+        h = leaky(_chain_np(np.broadcast_to(base[:, None, :], (N, S, w.proj_hidden)), w_p1[:, F_ + M:], e2))
+        x = _lin_np(n(w.w_p2), n(w.b_p2), h)
+        x = np.where((rows[:, :, 4] == f32(1))[:, :, None], x, f32(0)).astype(f32)
+        xg = _mean_rows_np(x)
+    return torch.from_numpy(np.ascontiguousarray(x)), torch.from_numpy(np.ascontiguousarray(xg))
+
+
+def _embed_torch(state: torch.Tensor, sf: torch.Tensor, w: EmbedWeights, S: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    F = torch.nn.functional
+    N, L, FM = state.shape[0], w.map_len, w.feat + w.map_feat
+    rows = state[:, :5 * S].reshape(N, S, 5)
+    hm = state[:, 5 * S + 9:5 * S + 9 + L * L].reshape(N, 1, L, L)
+    a = F.leaky_relu(F.conv2d(hm, w.w_conv1, w.b_conv1, stride=2, padding=1), w.slope)
+    a = F.leaky_relu(F.conv2d(a, w.w_conv2, w.b_conv2, stride=2, padding=1), w.slope)
+    fmap = F.leaky_relu(F.conv2d(a, w.w_conv3, w.b_conv3, stride=1, padding=1), w.slope).reshape(N, -1)
+    base = F.linear(torch.cat((sf, fmap), 1), w.w_p1[:, :FM], w.b_p1)         # once per bin, not once per row
+    e2 = F.linear(F.leaky_relu(F.linear(rows[:, :, :4], w.w_c1, w.b_c1), w.slope), w.w_c2, w.b_c2)
+    h = F.leaky_relu(F.linear(e2, w.w_p1[:, FM:]).add_(base[:, None, :]), w.slope)
+    x = F.linear(h, w.w_p2, w.b_p2)
+    x = torch.where((rows[:, :, 4] == 1)[:, :, None], x, torch.zeros((), dtype=x.dtype, device=x.device))
+    return x, x.mean(1)
+
+
+def _embed_rows(state: torch.Tensor, w: EmbedWeights) -> int:
+    """S of an observation block [N, obs_len] = 5 S + 9 + L^2 floats per row."""
+    if state.dim() != 2:
+        raise ValueError("state must be [N, obs_len]")
+    S, rest = divmod(int(state.shape[1]) - 9 - w.map_len ** 2, 5)
+    if rest != 0 or not 1 <= S <= EMBED_MAX_ROWS or state.shape[0] < 1:
+        raise ValueError(f"embed: obs_len = 5 S + 9 + {w.map_len}^2 with 1 <= S <= 1024, and at least one row")
+    return S
+
+
+@torch.no_grad()
+def embed(state: torch.Tensor, shape_feature: torch.Tensor, weights: EmbedWeights, *, use_hip: Optional[bool] = None,
+          out: Optional[torch.Tensor] = None, out_global: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The embedding stage of DQNBPP.forward without a gradient (model.py:318-326, :337-352, bufferSize == 1): the observation
+    ``state`` [N, obs_len] (a slice of a wider tensor passes as it is; S follows from obs_len and ``weights.map_len``) and
+    ``shape_feature`` [N, F] (shape_features' result) -> (``x`` float32 [N, S, E], ``x_global`` float32 [N, E]): the reference's
+    ``embeddings`` with the invalid rows zeroed and ``graph_embed``, what streams_greedy_action / streams_logits consume.
+    ``out`` / ``out_global``: float32 tensors of those shapes with contiguous rows (slices pass) to write into.  Defined
+    arithmetic (csrc/irbpp_embed.hip): every layer output one ascending fmaf chain from its bias, a convolution's over its
+    zero-padded taps in (c_in, ky, kx) order, project_layer[0]'s over (shape feature, map feature, candidate embedding) as over
+    the reference's concatenation -- its first F + M steps run once per bin, which changes no bit; a row whose mask is not
+    exactly 1 is +0.0; the mean is over all S rows in irbpp_dueling_act's summation.  On CPU tensors the exact numpy emulation
+    of the definition runs, on a HIP device with ``use_hip=True`` (``None`` takes EMBED_HIP_DEFAULT) the two launches of
+    irbpp_embed, else torch's layers in the same factored form (MIOpen's and rocBLAS's summation orders: close to, not
+    bit-equal with, the definition).  ``learn``'s forward with a gradient keeps torch's layers."""
+    w = weights
+    S = _embed_rows(state, w)
+    N, E = int(state.shape[0]), w.embed
+    dev = w.device
+    state = state.detach().to(device=dev, dtype=torch.float32)
+    if state.stride(1) != 1 or (N > 1 and state.stride(0) < state.shape[1]):
+        state = state.contiguous()
+    sf = shape_feature.detach().to(device=dev, dtype=torch.float32)
+    if tuple(sf.shape) != (N, w.feat):
+        raise ValueError(f"shape_feature must be [{N}, {w.feat}]")
+    if (w.feat > 1 and sf.stride(1) != 1) or (N > 1 and sf.stride(0) < w.feat):
+        sf = sf.contiguous()
+    if out is not None and (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (N, S, E) or
+                            (E > 1 and out.stride(2) != 1) or (S > 1 and out.stride(1) < E) or
+                            (N > 1 and out.stride(0) < (S - 1) * max(int(out.stride(1)), E) + E)):
+        raise ValueError(f"out must be a float32 [{N}, {S}, {E}] tensor on the weights' device with contiguous rows")
+    if out_global is not None and (out_global.dtype != torch.float32 or out_global.device != dev or
+                                   tuple(out_global.shape) != (N, E) or (E > 1 and out_global.stride(1) != 1) or
+                                   (N > 1 and out_global.stride(0) < E)):
+        raise ValueError(f"out_global must be a float32 [{N}, {E}] tensor on the weights' device with contiguous rows")
+    lib = _head_lib(w.w_p1, use_hip, EMBED_HIP_DEFAULT)
+    if lib is None:
+        x, xg = _embed_torch(state, sf, w, S) if dev.type == "cuda" else _embed_cpu(state, sf, w, S)
+        if out is not None:
+            x = out.copy_(x)
+        if out_global is not None:
+            xg = out_global.copy_(xg)
+        return x, xg
+    from . import _lib
+    if out is None:
+        out = torch.empty((N, S, E), dtype=torch.float32, device=dev)
+    if out_global is None:
+        out_global = torch.empty((N, E), dtype=torch.float32, device=dev)
+    row_stride = max(int(out.stride(1)), E) if S > 1 else E
+    env_stride = int(out.stride(0)) if N > 1 else (S - 1) * row_stride + E
+    ws = w._struct()
+    _lib.check(lib.irbpp_embed(C.byref(ws), _p(state), int(state.stride(0)) if N > 1 else int(state.shape[1]), _p(sf),
+                               int(sf.stride(0)) if N > 1 else w.feat, S, N, _p(w._base(N)), _p(out), env_stride, row_stride,
+                               _p(out_global), int(out_global.stride(0)) if N > 1 else E, _stream(dev)), "irbpp_embed")
+    return out, out_global
+
+
+@torch.no_grad()
+def network_greedy_action(state: torch.Tensor, points: ShapePoints, indices: torch.Tensor, shape_weights: ShapeEncoderWeights,
+                          embed_weights: EmbedWeights, stream_weights: StreamWeights, support: torch.Tensor, *,
+                          q_out: Optional[torch.Tensor] = None, use_hip: Optional[bool] = None) -> torch.Tensor:
+    """Agent.act from the observation (agent.py:51-58 with all of DQNBPP.forward, bufferSize == 1): ``state`` [N, obs_len] ->
+    int64[N], the three stages chained with no torch layer in between: shape_features on the id column ``state[:, 5 S]``,
+    embed, streams_greedy_action (which masks by the observation's validity flags).  ``indices``: the forward's one index set
+    (``points.draw_indices``); ``q_out`` as in streams_greedy_action; ``use_hip`` is handed to all three (``None``: each
+    one's own default; ``True``: the whole forward in the defined float32 arithmetic, bit for bit what the CPU form gives)."""
+    S = _embed_rows(state, embed_weights)
+    sf = shape_features(state[:, 5 * S], points, indices, shape_weights, use_hip=use_hip)
+    x, xg = embed(state, sf, embed_weights, use_hip=use_hip)
+    return streams_greedy_action(x, xg, stream_weights, support, state.to(x.device), q_out=q_out, use_hip=use_hip)
+
+
 def actor_step(envs, policy, memory: VectorReplayMemory, state: torch.Tensor, reward_clip: float = 0.0):
     """One iteration of the trainer's acting loop (trainer.py:160-186) without per-env Python:
     mask -> policy -> envs.step -> clip -> append.  ``envs`` is a GpuPackingEnv (device-tensor
