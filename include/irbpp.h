@@ -122,6 +122,10 @@ typedef struct {
 #define IRBPP_TUNE_NO_ROT_ALIAS 8388608 /* every rotation of an item builds its own observation, also where another rotation of the item has
                                          bit-identical footprint sizes, bottom table and ext_z_r (default: such a rotation reuses the other's
                                          drop heights and vertex bits, irbpp_rotalias.h); identical results, for A/B runs and the parity tests */
+#define IRBPP_TUNE_LDS_TILE 16777216 /* lattice data, observe-only transition launch (behind irbpp_apply_kernel): stage the float64 heightmap
+                                        tile in LDS as every other launch does (default there, on even grids with one action cell per thread:
+                                        each thread reduces its own action cell's heightmap cells in registers and writes their float32 copy,
+                                        no tile); identical results, for A/B runs and the parity tests                                    */
 #define IRBPP_TUNE_NO_SPECIALISED 1024 /* the run-time builds of the transition / emit kernels even where a build with the
                                          geometry as compile-time constants exists (16 x 16 action cells, step 2 or 4, R = 2 / 4 / 8,
                                          S = 500: BASELINE.json's configs); identical results, for A/B runs and the parity tests  */

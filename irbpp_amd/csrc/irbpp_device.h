@@ -179,6 +179,8 @@ struct Params {
                            // (one kernel per observation)
     int32_t vrow;          // words per rotation of w_valid (naiveMask bit rows): 16, or 32 on the capacity path
     int32_t rect;          // IRBPP_TUNE_RECT: isolated solid rectangles are answered by the transition kernel instead of the trace kernel (A/B)
+    int32_t lds_tile;      // IRBPP_TUNE_LDS_TILE: the observe-only lattice launch stages the heightmap tile in LDS like every other launch,
+                           // instead of reducing it in registers (cell_tile_stage in irbpp_kernels.hip) (A/B)
 };
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -298,6 +298,47 @@ __device__ __forceinline__ int tile_walk_index(const Params& P, const TileWalk& 
     return w.regular ? tile_row_part(P, w.row) + w.col_part : tile_of_linear(P, w.lin);
 }
 __device__ __forceinline__ void tile_walk_next(TileWalk& w) { w.lin += BLOCK; w.row += w.row_step; }
+// The observe-only lattice launch (MODE_OBSERVE on the block path, one action cell per thread, no padded planes) reads the
+// heightmap for two things: the maximum of every action cell's own STEP x STEP cells (L.c2, the first step of the block-max
+// grid) and the float32 copy in the observation.  Both are functions of what a thread holds after its loads when thread
+// t = X*Ay + Y loads action cell t's own cells: rows X*STEP + i, STEP contiguous doubles from column Y*STEP (a 16-byte load
+// at STEP 2; Ay neighbouring threads cover a heightmap row).  No LDS tile, no tile index arithmetic, no barrier of its own:
+// the maxima go to L.c2 in the order the planes are read in (overlap_test), the same doubles to the observation as float32.
+// (Hx == Ax*STEP and Hy == Ay*STEP where tile_words == Hc; STEP 2 and 4: Hy, Hc and the column are even -- 16-byte aligned.)
+template <int STEP>
+__device__ __forceinline__ void cell_tile_stage(const Params& P, double* c2, const double* ghm, float* obs, int tid) {
+    if (tid >= P.AC) return;
+    const int X = fdiv(tid, P.Ay, P.mg_ay), Y = tid - X * P.Ay;
+    const int at = X * STEP * P.Hy + Y * STEP;
+    const double* src = ghm + at;
+    float* dst = obs + 5 * P.S + 9 + at;
+    typedef double f64x2 __attribute__((ext_vector_type(2)));
+    double h[STEP][STEP];
+#pragma unroll
+    for (int i = 0; i < STEP; ++i) {
+        if constexpr (STEP == 1) {
+            h[i][0] = src[0];
+        } else {
+#pragma unroll
+            for (int j = 0; j < STEP; j += 2) {
+                const f64x2 v = *(const f64x2*)(src + i * P.Hy + j);
+                h[i][j] = v.x;
+                h[i][j + 1] = v.y;
+            }
+        }
+    }
+    double m = h[0][0];
+#pragma unroll
+    for (int i = 0; i < STEP; ++i)
+#pragma unroll
+        for (int j = 0; j < STEP; ++j)
+            if (i + j > 0) m = fmax(m, h[i][j]);
+    c2[tid] = m;
+#pragma unroll
+    for (int i = 0; i < STEP; ++i)
+#pragma unroll
+        for (int j = 0; j < STEP; ++j) dst[i * P.Hy + j] = (float)h[i][j];
+}
 #if IRBPP_PASS == 1
 // footprint cell `ij` (i | j << 16) of an item whose corner sits on action cell (lx, ly)
 __device__ __forceinline__ int tile_of_cell(const Params& P, int lx, int ly, int ij) {
@@ -896,7 +937,8 @@ __device__ inline void gcell_walk(ConstGCellPtr gc, int nb, const char* const (&
 #endif  // IRBPP_PASS == 1
 template <int PATH>
 __device__ inline int overlap_test(const Params& P, const Tables& T, const State& S, const StepIO& io,
-                                   const Lds& L, int b, int item, bool debug_out, double* zdst, bool sr_staged, bool dense) {
+                                   const Lds& L, int b, int item, bool debug_out, double* zdst, bool sr_staged, bool dense,
+                                   bool c2_ready = false) {
     const bool use_block = PATH == PATH_BLOCK || PATH == PATH_MIXED || (PATH == PATH_ANY && P.block_b > 0);
     const bool use_box = PATH == PATH_BOX || (PATH == PATH_ANY && P.box != 0);
     // rotations that take the block loop (all of them on pure lattice data); the others walk their cell lists below
@@ -928,14 +970,17 @@ __device__ inline int overlap_test(const Params& P, const Tables& T, const State
         // in the phase-plane layout those are entry X*Ay + Y of every plane -- step^2 conflict-free reads at one index.
         // (2) a b x b block is (b / step)^2 neighbouring action cells.  (Reading the b^2 cells of every block straight from
         // the planes took 16 scattered reads with their index arithmetic per block at b = 4, step = 2.)
+        // (c2_ready: the observe-only launch has no tile; every thread wrote its own cell's entry from registers, in front of the
+        // caller's barrier -- cell_tile_stage.  ShapeRots this function had to load itself still need a barrier before they are read.)
         const int planes = P.pp * P.pp, mq = P.block_b / P.step;
+        if (!c2_ready)
 #pragma unroll 1
         for (int t = tid; t < AC; t += BLOCK) {
             double m = L.hm[t];
             for (int pl = 1; pl < planes; ++pl) m = fmax(m, L.hm[pl * P.PL + t]);
             L.c2[t] = m;
         }
-        __syncthreads();
+        if (!c2_ready || (item >= 0 && !sr_staged)) __syncthreads();
         // The item's block lists -- all rotations, contiguous in the table, a few dozen 16-byte entries -- are requested now, a
         // thread per entry: they arrive during the grid's second step and go to LDS behind it (the bytes of c2, dead by then),
         // where the rotation loops read them with ONE broadcast ds_read_b128 per entry instead of three v_readlane.
@@ -1388,16 +1433,18 @@ __device__ inline void split_handover(const Params& P, const State& S, const Lds
 template <int PATH, bool CHAIN = false>
 __device__ inline void observe_location(const Params& P, const Tables& T, const State& S, const StepIO& io,
                                         const Lds& L, int b, int item, float* obs, bool debug_out, bool sr_staged,
-                                        unsigned char* chain_lds = nullptr) {
+                                        unsigned char* chain_lds = nullptr, bool cell_tile = false) {
     item = __builtin_amdgcn_readfirstlane(item);     // block-uniform: footprint reads become scalar loads
     const int tid = threadIdx.x;
     const int R = P.R, AC = P.AC, Ax = P.Ax, Ay = P.Ay;
     const int X = fdiv(tid, Ay, P.mg_ay), Y = tid - X * Ay;
-    const int nvalid = IRBPP_HERE overlap_test<PATH>(P, T, S, io, L, b, item, debug_out, S.w_posz + (size_t)b * R * AC, sr_staged, false);
+    const int nvalid = IRBPP_HERE overlap_test<PATH>(P, T, S, io, L, b, item, debug_out, S.w_posz + (size_t)b * R * AC, sr_staged, false, cell_tile);
     if (debug_out) return;
     // the tile is done with: write its float32 copy and the item vector now, because the
     // contour scratch and the candidate keys reuse the tile's LDS
+    // (cell_tile: there is no tile, and the float32 copy went out with the loads -- cell_tile_stage)
     if (tid < 9) obs[5 * P.S + tid] = tid == 0 ? (float)item : 0.0f;
+    if (!cell_tile)
     for (int rep = 0; rep < IRBPP_REPS(8); ++rep)
     for (TileWalk w = IRBPP_HERE tile_walk_begin(P, tid); w.lin < P.Hc; tile_walk_next(w)) obs[5 * P.S + 9 + w.lin] = (float)L.hm[tile_walk_index(P, w)];
     __syncthreads();
@@ -2790,10 +2837,17 @@ __device__ __forceinline__ void env_transition(const Params& P_run, const Tables
         st_cursor = ps0->cursor;
         st_trow = ps0->traj_row;
     }
-    // stage the heightmap tile
+    // stage the heightmap tile -- or, where the launch only observes lattice data, no tile at all (cell_tile_stage; the old
+    // form stays reachable: IRBPP_TUNE_LDS_TILE)
+    const bool cell_tile = PATH == PATH_BLOCK && !CHAIN && mode == MODE_OBSERVE && P.lds_tile == 0 && P.tile_words == P.Hc &&
+                           P.AC <= BLOCK && (P.step == 1 || P.step == 2 || P.step == 4);
     if (mode == MODE_RESET) {
         for (int i = tid; i < P.tile_words; i += BLOCK) L.hm[i] = 0.0;
         for (int i = tid; i < P.Hc; i += BLOCK) ghm[i] = 0.0;
+    } else if (cell_tile) {
+        if (P.step == 2) IRBPP_HERE cell_tile_stage<2>(P, L.c2, ghm, obs, tid);
+        else if (P.step == 4) IRBPP_HERE cell_tile_stage<4>(P, L.c2, ghm, obs, tid);
+        else IRBPP_HERE cell_tile_stage<1>(P, L.c2, ghm, obs, tid);
     } else {
         if (P.tile_words > P.Hc) {                       // odd action grid: the planes have padding entries
             for (int i = tid; i < P.tile_words; i += BLOCK) L.hm[i] = 0.0;
@@ -3070,7 +3124,7 @@ __device__ __forceinline__ void env_transition(const Params& P_run, const Tables
             for (int i = tid; i < P.Hc; i += BLOCK) obs[P.K + i] = (float)L.hm[tile_of_linear(P, i)];
         }
     }
-    if (do_observe) IRBPP_HERE observe_location<PATH, CHAIN>(P, T, S, io, L, b, obs_item, obs, debug_out, sr_staged, smem + P.lds_bytes);
+    if (do_observe) IRBPP_HERE observe_location<PATH, CHAIN>(P, T, S, io, L, b, obs_item, obs, debug_out, sr_staged, smem + P.lds_bytes, cell_tile);
 }
 
 #if IRBPP_PASS == 1

@@ -137,6 +137,9 @@ inline int pick_spec(const Params& P, int tuning) {
 // group of bins on another stream the split pays a round earlier (BlockOut as two groups of 4096: 59.1 -> 60.5 M,
 // profiles/r05/s10).  Hence, for online steps: lattice and box data from two rounds of workgroups on, cell lists from four
 // rounds on where eight workgroups share a CU.
+// (Re-measured with the observe-only lattice launch reducing the heightmap in registers, profiles/register_tile: BlockOut as one
+// group, split vs fused at 2048 / 3072 / 4096 bins -3.1 % / +2.6 % / +3.0 % -- the crossover now lies between one and one and a
+// half rounds.  The threshold stays at two rounds: one run per point, and tests/test_launch_plan_host.py pins it.)
 inline bool split_apply(const Params& P, int tuning, int n) {
     if (P.stability != 0 || (tuning & IRBPP_TUNE_FUSED_APPLY)) return false;
     if (tuning & IRBPP_TUNE_SPLIT_APPLY) return true;
