@@ -754,6 +754,48 @@ int irbpp_embed(const irbpp_embed_weights* w, const float* obs_dev, int64_t obs_
                 int64_t feat_stride, int32_t s_rows, int32_t n_env, float* base_dev /* workspace [n_env][proj_hidden] */,
                 float* x_dev, int64_t env_stride, int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream);
 
+/* The layers of the order network's embedding stage (model.py, bufferSize > 1: heightEncoder as above; gat_project_layer =
+ * Linear(feat + c3 (map_len/4)^2, proj_hidden) LeakyReLU Linear(proj_hidden, embed); embedder = GraphAttentionEncoder with
+ * one head and one layer: W_query, W_key, W_val Linear(embed, embed) without a bias, W_out Linear(embed, embed), the
+ * feed-forward pair Linear(embed, ff_hidden) ReLU Linear(ff_hidden, embed)), float32 on the device, contiguous, in torch's
+ * layouts.  w_g1 keeps the reference's columns: [0 .. feat) the shape feature, [feat ..) the map feature. */
+typedef struct { const float *w_conv1, *b_conv1, *w_conv2, *b_conv2, *w_conv3, *b_conv3,
+                 *w_g1, *b_g1, *w_g2, *b_g2, *w_q, *w_k, *w_v, *w_o, *b_o, *w_f1, *b_f1, *w_f2, *b_f2;
+                 int32_t map_len, c1, c2, c3, feat, proj_hidden, embed, ff_hidden; float slope; } irbpp_order_embed_weights;
+/* replaces: the embedding stage of DQNBPP.forward without a gradient for bufferSize > 1 (model.py:355-383,
+ * embed_k_buffer_shape_with_gat, with :26-171 and :284-294; the order network of trainer_hierarchical, trainer.py:266): the
+ * heightmap CNN, the [n_env * k_slots][feat + M] concatenation, both layers of gat_project_layer, Q / K / V, the two batched
+ * k x k matmuls, the softmax, the clone and masked assignment (the mask is all zeros on this path and does not enter), W_out,
+ * the feed-forward pair, the two residual adds and the mean.  Two launches on `stream`, no atomics: the map part of every
+ * gat_project_layer[0] chain runs once per bin into base_dev; then tiles of 64 / k_slots whole bins, one (bin, slot) row
+ * per lane; Q, K, V, the compatibilities and every hidden block stay in LDS and registers.
+ * obs_dev float32 [n_env][obs_stride]: obs[0 .. k_slots) the buffered item ids (not read), obs[k_slots ..] the map_len x
+ * map_len heightmap, row-major; shape_feat_dev float32 [n_env * k_slots][feat], bin-major, (bin, slot) rows feat_stride
+ * floats apart (irbpp_shape_features' out over the n_env * k_slots ids); base_dev float32 [n_env][proj_hidden], a
+ * workspace; x_dev float32 [n_env][k_slots][embed], row i of env e at x_dev + e*env_stride + i*row_stride; xg_dev float32
+ * [n_env][embed], rows xg_stride floats apart: what irbpp_streams_act takes as x_dev and xg_dev with s_rows = k_slots and
+ * obs_dev = NULL.
+ * The float32 arithmetic is defined (csrc/irbpp_order_embed.hip): every output of a layer is one chain acc = start; acc =
+ * fmaf(x[c], W[j][c], acc) for c ascending, a single-rounding fused multiply-add, never split or re-associated; leaky(s) =
+ * s > 0 ? s : slope * s, relu(s) = s > 0 ? s : +0; the CNN as in irbpp_embed.  gat_project_layer[0]'s chain starts from its
+ * bias, runs over the map feature against columns [feat ..) FIRST (once per bin) and then over the slot's shape feature
+ * against columns [0 .. feat): a fixed permutation of the concatenation's summation order.  h0 = gat_project_layer[1] (no
+ * activation).  Q, K, V are chains from +0.0; c[i][j] = nf * (the chain from +0.0 of fmaf(Q[i][d], K[j][d], acc), d
+ * ascending) with nf = (float)(1.0 / sqrt((double)embed)); m = max_j c[i][j], e[j] = exp(c[i][j] - m) by irbpp_dueling_act's
+ * exp, den the e[j] added left to right from 0.0, a[i][j] = e[j] / den; hd[i][d] the chain from +0.0 of fmaf(a[i][j],
+ * V[j][d], acc), j ascending; h1 = h0 + lin(W_out, hd); h2 = h1 + lin(ff2, relu(lin(ff1, h1))); x = h2 and xg the mean of
+ * the k_slots rows in irbpp_dueling_act's summation (16 interleaved partial sums added left to right, divided by
+ * (float)k_slots).  Reproducible bit for bit whatever n_env, the strides and the tiles; no index depends on data, so nothing
+ * is accessed out of range whatever the values.  Inputs must be finite: a NaN gives unspecified values.
+ * IRBPP_ERR_ARG unless map_len is a multiple of 4 in [8, 32], 1 <= c1 <= 16, 1 <= c2 <= 32, 1 <= c3 <= 4, 1 <= feat,
+ * proj_hidden, embed, ff_hidden <= 256, slope >= 0, 2 <= k_slots <= 64, n_env >= 1, obs_stride >= k_slots + map_len^2,
+ * feat_stride >= feat, row_stride >= embed, env_stride >= (k_slots-1)*row_stride + embed, xg_stride >= embed and no pointer
+ * is NULL. */
+int irbpp_order_embed(const irbpp_order_embed_weights* w, const float* obs_dev, int64_t obs_stride,
+                      const float* shape_feat_dev, int64_t feat_stride /* between (bin, slot) rows */,
+                      int32_t k_slots, int32_t n_env, float* base_dev /* workspace [n_env][proj_hidden] */,
+                      float* x_dev, int64_t env_stride, int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream);
+
 /* Tooling: when cycles_dev != NULL every later transition launch stores, per bin, one row
  * int64[num_bins][16]: shader-clock stamps 0 start, 1 action applied, 2 overlap test done,
  * 3 contour stage done, 4 observation written; 5..7 contour-stage detail; 8/9 the 100 MHz wall

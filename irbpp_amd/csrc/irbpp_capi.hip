@@ -29,6 +29,7 @@
 #include "irbpp_streams.hip"        // the four noisy layers of the value and advantage streams in front of the dueling head (irbpp_noisy_weights, irbpp_streams_act)
 #include "irbpp_shapefeat.hip"      // the shape branch in front of the network: sampled points to shape features (irbpp_shape_features)
 #include "irbpp_embed.hip"          // the embedding stage: heightmap CNN, candidate rows, masked mean (irbpp_embed)
+#include "irbpp_order_embed.hip"    // the order network's embedding stage: CNN, k buffered items, one attention layer, mean (irbpp_order_embed)
 #include "irbpp_metrics.hip"        // the trainer's episode metrics (irbpp_set_episode_window)
 #include "irbpp_itemgen.h"
 #include "irbpp_plan.h"             // which kernels a transition launches: the registry of kernels and plan_transition
@@ -1312,6 +1313,37 @@ int irbpp_embed(const irbpp_embed_weights* w, const float* obs_dev, int64_t obs_
         return IRBPP_ERR_HIP;
     hipLaunchKernelGGL(irbpp_embed_rows_kernel, dim3(n_env), dim3(EMBED_ROW_THREADS), lds, (hipStream_t)stream, w->w_c1, w->b_c1,
                        w->w_c2, w->b_c2, w->w_p1, w->w_p2, w->b_p2, obs_dev, (const float*)base_dev, x_dev, xg_dev, g);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+int irbpp_order_embed(const irbpp_order_embed_weights* w, const float* obs_dev, int64_t obs_stride, const float* shape_feat_dev,
+                      int64_t feat_stride, int32_t k_slots, int32_t n_env, float* base_dev, float* x_dev, int64_t env_stride,
+                      int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream) {
+    if (!w || !w->w_conv1 || !w->b_conv1 || !w->w_conv2 || !w->b_conv2 || !w->w_conv3 || !w->b_conv3 || !w->w_g1 || !w->b_g1 ||
+        !w->w_g2 || !w->b_g2 || !w->w_q || !w->w_k || !w->w_v || !w->w_o || !w->b_o || !w->w_f1 || !w->b_f1 || !w->w_f2 ||
+        !w->b_f2 || !obs_dev || !shape_feat_dev || !base_dev || !x_dev || !xg_dev || w->map_len < 8 ||
+        w->map_len > EMBED_MAX_MAP || w->map_len % 4 != 0 || w->c1 < 1 || w->c1 > EMBED_MAX_C1 || w->c2 < 1 ||
+        w->c2 > EMBED_MAX_C2 || w->c3 < 1 || w->c3 > EMBED_MAX_C3 || w->feat < 1 || w->feat > ORDER_MAX_WIDTH ||
+        w->proj_hidden < 1 || w->proj_hidden > ORDER_MAX_WIDTH || w->embed < 1 || w->embed > ORDER_MAX_WIDTH ||
+        w->ff_hidden < 1 || w->ff_hidden > ORDER_MAX_WIDTH || !(w->slope >= 0.0f) || k_slots < 2 || k_slots > ORDER_MAX_SLOTS ||
+        n_env < 1 || obs_stride < (int64_t)k_slots + (int64_t)w->map_len * w->map_len || feat_stride < w->feat ||
+        row_stride < w->embed || env_stride < (int64_t)(k_slots - 1) * row_stride + w->embed || xg_stride < w->embed)
+        return IRBPP_ERR_ARG;
+    OrderEmbedArgs g;
+    g.obs_stride = obs_stride, g.feat_stride = feat_stride, g.env_stride = env_stride, g.row_stride = row_stride, g.xg_stride = xg_stride;
+    g.map_len = w->map_len, g.c1 = w->c1, g.c2 = w->c2, g.c3 = w->c3, g.feat = w->feat, g.proj_hidden = w->proj_hidden;
+    g.embed = w->embed, g.ff_hidden = w->ff_hidden, g.k_slots = k_slots, g.n_env = n_env, g.slope = w->slope;
+    g.norm = (float)(1.0 / sqrt((double)w->embed));
+    hipLaunchKernelGGL(irbpp_order_bin_kernel, dim3(n_env), dim3(EMBED_BIN_THREADS), 0, (hipStream_t)stream, w->w_conv1, w->b_conv1,
+                       w->w_conv2, w->b_conv2, w->w_conv3, w->b_conv3, w->w_g1, w->b_g1, obs_dev, base_dev, g);
+    if (hipGetLastError() != hipSuccess) return IRBPP_ERR_HIP;
+    const size_t lds = (size_t)order_rows_lds_floats(w->feat, w->proj_hidden, w->embed, w->ff_hidden, k_slots) * sizeof(float);
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)irbpp_order_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)lds) != hipSuccess)
+        return IRBPP_ERR_HIP;
+    hipLaunchKernelGGL(irbpp_order_rows_kernel, dim3(order_tiles(n_env, k_slots)), dim3(EMBED_ROW_THREADS), lds, (hipStream_t)stream,
+                       w->w_g1, w->w_g2, w->b_g2, w->w_q, w->w_k, w->w_v, w->w_o, w->b_o, w->w_f1, w->b_f1, w->w_f2, w->b_f2,
+                       shape_feat_dev, (const float*)base_dev, x_dev, xg_dev, g);
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
 }
 

@@ -1444,6 +1444,286 @@ def network_greedy_action(state: torch.Tensor, points: ShapePoints, indices: tor
     return streams_greedy_action(x, xg, stream_weights, support, state.to(x.device), q_out=q_out, use_hip=use_hip)
 
 
+# The same question for the order network's embedding stage ("The order network"): torch's layers in the
+# factored form or the two launches of irbpp_order_embed.  Torch's layers, since tools/order_embed_rates.py measured on an
+# MI355X, k = 10: 0.80 ms against 1.19 ms for the kernels at 4096 bins (spreads 0.01 ms) and 0.50 against 0.39 ms at 1024
+# (spreads 0.05 / 0.01 ms): the kernels win at one size only, and the default changes only for a win beyond the larger spread
+# at both (profiles/order_embed/).  The reference's lines with their host gather: 135 and 27 ms.  Measured for the stage from
+# a given shape feature; the whole acting forward: 1.04 / 0.73 ms with every stage's default, 4.78 / 1.38 ms with
+# use_hip=True throughout (irbpp_streams_act is most of that).  Not measured: other k, and bins below 1024.
+# use_hip=True asks for the kernels (the reproducible forward).
+ORDER_EMBED_HIP_DEFAULT = False
+
+ORDER_MAX_WIDTH, ORDER_MAX_SLOTS = 256, 64
+_ORDER_FIELDS = ("w_conv1", "b_conv1", "w_conv2", "b_conv2", "w_conv3", "b_conv3", "w_g1", "b_g1", "w_g2", "b_g2", "w_q", "w_k", "w_v",
+                 "w_o", "b_o", "w_f1", "b_f1", "w_f2", "b_f2")
+_ORDER_SIZES = ("map_len", "c1", "c2", "c3", "feat", "proj_hidden", "embed", "ff_hidden")
+
+
+class _IrbppOrderEmbedWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in _ORDER_FIELDS] + [(n, C.c_int32) for n in _ORDER_SIZES] + [("slope", C.c_float)]
+
+
+class OrderEmbedWeights(object):
+    """The layers of the order network's embedding stage (DQNBPP with bufferSize > 1) as float32 contiguous tensors in torch's
+    layouts: ``heightEncoder``'s three Conv2d, ``gat_project_layer``'s two Linear and ``embedder``, a GraphAttentionEncoder of
+    one layer and one head, read as ``embedder.layers[0]``: ``[0].module`` gives ``W_query``, ``W_key``, ``W_val`` (no bias)
+    and ``W_out``, ``[1].module`` the feed-forward pair Linear ReLU Linear.  Raises on ``n_heads != 1``, on more than one
+    layer, on an ``init_embed`` and on widths that do not line up.  ``map_len`` is the heightmap's side L, from which the
+    shape feature's width follows: F = gat_project_layer[0].in_features - c3 (L/4)^2.  Copies: call ``refresh()`` after every
+    optimiser step."""
+
+    def __init__(self, height_encoder, gat_project_layer, embedder, negative_slope: float = 0.01, *, map_len: int = 32):
+        convs = [m for m in height_encoder if getattr(m, "weight", None) is not None and m.weight.dim() == 4]
+        projs = [m for m in gat_project_layer if getattr(m, "weight", None) is not None and m.weight.dim() == 2]
+        if len(convs) != 3 or len(projs) != 2:
+            raise ValueError("order_embed: three Conv2d and two Linear (gat_project_layer)")
+        if getattr(embedder, "init_embed", None) is not None:
+            raise ValueError("order_embed: an embedder with an init_embed is not supported")
+        layers = list(embedder.layers)
+        if len(layers) != 1:
+            raise ValueError("order_embed: one attention layer")
+        att, ff = layers[0][0].module, layers[0][1].module
+        if int(getattr(att, "n_heads", 1)) != 1:
+            raise ValueError("order_embed: one attention head")
+        ffs = [m for m in ff if getattr(m, "weight", None) is not None and m.weight.dim() == 2] if hasattr(ff, "__iter__") else []
+        if len(ffs) != 2:
+            raise ValueError("order_embed: the feed-forward pair Linear ReLU Linear")
+        qkv = (att.W_query, att.W_key, att.W_val)
+        if any(getattr(m, "bias", None) is not None for m in qkv):
+            raise ValueError("order_embed: W_query, W_key and W_val have no bias")
+        self.layers = tuple(convs + projs) + qkv + (att.W_out,) + tuple(ffs)
+        if any(m.bias is None for m in convs + projs + [att.W_out] + ffs):
+            raise ValueError("order_embed: every other layer has a bias")
+        self.slope, self.map_len = float(negative_slope), int(map_len)
+        for m, (ks, s, p) in zip(convs, ((4, 2, 1), (4, 2, 1), (3, 1, 1))):
+            if tuple(m.weight.shape[2:]) != (ks, ks) or tuple(getattr(m, "stride", (s, s))) != (s, s) or \
+                    tuple(getattr(m, "padding", (p, p))) != (p, p):
+                raise ValueError("order_embed: Conv2d(1, c1, 4, 2, 1), Conv2d(c1, c2, 4, 2, 1), Conv2d(c2, c3, 3, 1, 1)")
+        self.c1, self.c2, self.c3 = (int(m.weight.shape[0]) for m in convs)
+        self.proj_hidden, self.embed = int(projs[0].weight.shape[0]), int(projs[1].weight.shape[0])
+        self.ff_hidden = int(ffs[0].weight.shape[0])
+        if self.map_len % 4 != 0 or not 8 <= self.map_len <= 32:
+            raise ValueError("order_embed: map_len is a multiple of 4 in [8, 32]")
+        self.map_feat = self.c3 * (self.map_len // 4) ** 2
+        self.feat = int(projs[0].weight.shape[1]) - self.map_feat
+        E = self.embed
+        want = [(self.c1, 1, 4, 4), (self.c2, self.c1, 4, 4), (self.c3, self.c2, 3, 3), (self.proj_hidden, self.feat + self.map_feat),
+                (E, self.proj_hidden), (E, E), (E, E), (E, E), (E, E), (self.ff_hidden, E), (E, self.ff_hidden)]
+        for m, shape in zip(self.layers, want):
+            if tuple(m.weight.shape) != shape or (m.bias is not None and tuple(m.bias.shape) != shape[:1]):
+                raise ValueError(f"order_embed: a weight of shape {tuple(m.weight.shape)} beside the expected {shape}")
+        if not (1 <= self.c1 <= 16 and 1 <= self.c2 <= 32 and 1 <= self.c3 <= 4 and self.slope >= 0 and
+                all(1 <= v <= ORDER_MAX_WIDTH for v in (self.feat, self.proj_hidden, E, self.ff_hidden))):
+            raise ValueError("order_embed: 1 <= c1 <= 16, 1 <= c2 <= 32, 1 <= c3 <= 4, 1 <= feat, proj_hidden, embed, ff_hidden <= 256 "
+                             "and negative_slope >= 0")
+        import numpy as np
+        self.norm = float(np.float32(1.0 / np.sqrt(np.float64(E))))     # nf: 1 / sqrt(E) in float64, rounded to float32 once
+        self.device = convs[0].weight.device
+        self._workspace = {}
+        self.refresh()
+
+    @classmethod
+    def from_layers(cls, height_encoder, gat_project_layer, embedder, negative_slope: float = 0.01, *,
+                    map_len: int = 32) -> "OrderEmbedWeights":
+        return cls(height_encoder, gat_project_layer, embedder, negative_slope, map_len=map_len)
+
+    @torch.no_grad()
+    def refresh(self) -> "OrderEmbedWeights":
+        names = iter(_ORDER_FIELDS)
+        for m in self.layers:
+            setattr(self, next(names), _f32(m.weight.detach(), self.device).clone())
+            if m.bias is not None:
+                setattr(self, next(names), _f32(m.bias.detach(), self.device).clone())
+        return self
+
+    def _struct(self) -> _IrbppOrderEmbedWeights:
+        return _IrbppOrderEmbedWeights(*(getattr(self, n).data_ptr() for n in _ORDER_FIELDS), *(getattr(self, n) for n in _ORDER_SIZES),
+                                       self.slope)
+
+    def _base(self, n_env: int) -> torch.Tensor:
+        if n_env not in self._workspace:
+            self._workspace = {n_env: torch.empty((n_env, self.proj_hidden), dtype=torch.float32, device=self.device)}
+        return self._workspace[n_env]
+
+
+def _dexp_np(t):
+    """dueling_dexp (csrc/irbpp_head.h) on a float32 numpy array of arguments <= 0: exactly 0 below -80."""
+    import numpy as np
+    f32 = np.float32
+    tc = np.maximum(t.astype(f32), f32(-80.0))
+    n = np.floor(tc * f32(1.4426950408889634) + f32(0.5))
+    r = (tc - n * f32(0.693145751953125)) - n * f32(1.4286068203094172e-06)
+    p = np.full(tc.shape, f32(1.9841269841269841e-04), dtype=f32)
+    for c in (1.3888888888888889e-03, 8.3333333333333332e-03, 4.1666666666666664e-02, 1.6666666666666666e-01, 0.5, 1.0, 1.0):
+        p = p * r + f32(c)
+    scale = ((n.astype(np.int32) + 127) << 23).astype(np.uint32).view(f32)
+    return np.where(t < f32(-80.0), f32(0), p * scale).astype(f32)
+
+
+def _order_embed_cpu(state: torch.Tensor, sf: torch.Tensor, w: OrderEmbedWeights, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    import numpy as np
+    f32 = np.float32
+    n = lambda t: t.detach().to(torch.float32).cpu().numpy()  # noqa: E731
+    leaky = lambda s: np.where(s > 0, s, f32(w.slope) * s).astype(f32)  # noqa: E731
+    relu = lambda s: np.where(s > 0, s, f32(0)).astype(f32)  # noqa: E731
+    obs, sf = n(state), n(sf)
+    N, L, F_, M, E = obs.shape[0], w.map_len, w.feat, w.map_feat, w.embed
+    with np.errstate(all="ignore"):
+        hm = obs[:, k:k + L * L].reshape(N, 1, L, L)
+        a = leaky(_conv_np(hm, n(w.w_conv1), n(w.b_conv1), 2, 1))
+        a = leaky(_conv_np(a, n(w.w_conv2), n(w.b_conv2), 2, 1))
+        fmap = leaky(_conv_np(a, n(w.w_conv3), n(w.b_conv3), 1, 1)).reshape(N, M)
+        w_g1 = n(w.w_g1)
+        base = _chain_np(np.broadcast_to(n(w.b_g1), (N, w.proj_hidden)).astype(f32), w_g1[:, F_:], fmap)     # the map goes first
+        g = leaky(_chain_np(np.broadcast_to(base[:, None, :], (N, k, w.proj_hidden)), w_g1[:, :F_], sf))
+        h0 = _lin_np(n(w.w_g2), n(w.b_g2), g)
+        zero = np.zeros((E,), dtype=f32)
+        q, key, v = (_lin_np(n(t), zero, h0) for t in (w.w_q, w.w_k, w.w_v))
+        c = np.zeros((N, k, k), dtype=f32)
+        for d in range(E):
+            c = _fmaf_np(q[:, :, None, d], key[:, None, :, d], c)
+        c = (f32(w.norm) * c).astype(f32)
+        e = _dexp_np(c - c.max(-1, keepdims=True))
+        den = np.zeros((N, k), dtype=f32)
+        for j in range(k):
+            den = den + e[:, :, j]
+        att = (e / den[:, :, None]).astype(f32)
+        hd = np.zeros((N, k, E), dtype=f32)
+        for j in range(k):
+            hd = _fmaf_np(att[:, :, j:j + 1], v[:, j:j + 1, :], hd)
+        h1 = h0 + _lin_np(n(w.w_o), n(w.b_o), hd)
+        x = h1 + _lin_np(n(w.w_f2), n(w.b_f2), relu(_lin_np(n(w.w_f1), n(w.b_f1), h1)))
+        xg = _mean_rows_np(x)
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=f32)), torch.from_numpy(np.ascontiguousarray(xg, dtype=f32))
+
+
+def _order_embed_torch(state: torch.Tensor, sf: torch.Tensor, w: OrderEmbedWeights, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    F = torch.nn.functional
+    N, L, F_ = state.shape[0], w.map_len, w.feat
+    hm = state[:, k:k + L * L].reshape(N, 1, L, L)
+    a = F.leaky_relu(F.conv2d(hm, w.w_conv1, w.b_conv1, stride=2, padding=1), w.slope)
+    a = F.leaky_relu(F.conv2d(a, w.w_conv2, w.b_conv2, stride=2, padding=1), w.slope)
+    fmap = F.leaky_relu(F.conv2d(a, w.w_conv3, w.b_conv3, stride=1, padding=1), w.slope).reshape(N, -1)
+    base = F.linear(fmap, w.w_g1[:, F_:], w.b_g1)                                # once per bin, not once per slot
+    h0 = F.linear(F.leaky_relu(F.linear(sf, w.w_g1[:, :F_]).add_(base[:, None, :]), w.slope), w.w_g2, w.b_g2)
+    q, key, v = F.linear(h0, w.w_q), F.linear(h0, w.w_k), F.linear(h0, w.w_v)
+    att = torch.softmax(w.norm * torch.matmul(q, key.transpose(1, 2)), dim=-1)
+    h1 = h0 + F.linear(torch.matmul(att, v), w.w_o, w.b_o)
+    x = h1 + F.linear(F.relu(F.linear(h1, w.w_f1, w.b_f1)), w.w_f2, w.b_f2)
+    return x, x.mean(1)
+
+
+def _order_slots(state: torch.Tensor, w: OrderEmbedWeights) -> int:
+    """k of an order observation block [N, obs_len] = k + L^2 floats per row."""
+    if state.dim() != 2:
+        raise ValueError("state must be [N, obs_len]")
+    k = int(state.shape[1]) - w.map_len ** 2
+    if not 2 <= k <= ORDER_MAX_SLOTS or state.shape[0] < 1:
+        raise ValueError(f"order_embed: obs_len = k + {w.map_len}^2 with 2 <= k <= 64, and at least one row")
+    return k
+
+
+@torch.no_grad()
+def order_embed(state: torch.Tensor, shape_feature: torch.Tensor, weights: OrderEmbedWeights, *, use_hip: Optional[bool] = None,
+                out: Optional[torch.Tensor] = None, out_global: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The embedding stage of the order network, DQNBPP.forward without a gradient for bufferSize > 1 (model.py:355-383): the
+    order observation ``state`` [N, k + L^2] (k buffered item ids, then the heightmap; a slice of a wider tensor passes as it
+    is; k follows from obs_len and ``weights.map_len``) and ``shape_feature`` [N*k, F] or [N, k, F] (shape_features over the
+    N k ids, bin-major) -> (``x`` float32 [N, k, E], ``x_global`` float32 [N, E]): the reference's ``embeddings`` and
+    ``graph_embed``, what streams_greedy_action consumes with ``state=None``.  ``out`` / ``out_global`` as in embed.  Defined
+    arithmetic (csrc/irbpp_order_embed.hip): every layer output one ascending fmaf chain; gat_project_layer[0]'s runs over the
+    map feature first (once per bin) and then over the slot's shape feature -- a fixed permutation of the reference's
+    concatenation order; one attention head without a mask, its softmax with irbpp_dueling_act's exp; the mean in its
+    summation.  On CPU tensors the exact numpy emulation of the definition runs, on a HIP device with ``use_hip=True``
+    (``None`` takes ORDER_EMBED_HIP_DEFAULT) the two launches of irbpp_order_embed, else torch's layers in the same factored
+    form (close to, not bit-equal with, the definition).  ``learn``'s forward with a gradient keeps torch's layers."""
+    w = weights
+    k = _order_slots(state, w)
+    N, E, F_ = int(state.shape[0]), w.embed, w.feat
+    dev = w.device
+    state = state.detach().to(device=dev, dtype=torch.float32)
+    if state.stride(1) != 1 or (N > 1 and state.stride(0) < state.shape[1]):
+        state = state.contiguous()
+    sf = shape_feature.detach().to(device=dev, dtype=torch.float32)
+    if tuple(sf.shape) not in ((N * k, F_), (N, k, F_)):
+        raise ValueError(f"shape_feature must be [{N * k}, {F_}] or [{N}, {k}, {F_}]")
+    if sf.dim() == 3:
+        sf = sf.reshape(N * k, F_)                       # a view where the strides allow it, else a copy
+    if (F_ > 1 and sf.stride(1) != 1) or sf.stride(0) < F_:
+        sf = sf.contiguous()
+    if out is not None and (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (N, k, E) or
+                            (E > 1 and out.stride(2) != 1) or out.stride(1) < E or
+                            (N > 1 and out.stride(0) < (k - 1) * int(out.stride(1)) + E)):
+        raise ValueError(f"out must be a float32 [{N}, {k}, {E}] tensor on the weights' device with contiguous rows")
+    if out_global is not None and (out_global.dtype != torch.float32 or out_global.device != dev or
+                                   tuple(out_global.shape) != (N, E) or (E > 1 and out_global.stride(1) != 1) or
+                                   (N > 1 and out_global.stride(0) < E)):
+        raise ValueError(f"out_global must be a float32 [{N}, {E}] tensor on the weights' device with contiguous rows")
+    lib = _head_lib(w.w_g1, use_hip, ORDER_EMBED_HIP_DEFAULT)
+    if lib is None:
+        x, xg = _order_embed_torch(state, sf.reshape(N, k, F_), w, k) if dev.type == "cuda" else \
+            _order_embed_cpu(state, sf.reshape(N, k, F_), w, k)
+        if out is not None:
+            x = out.copy_(x)
+        if out_global is not None:
+            xg = out_global.copy_(xg)
+        return x, xg
+    from . import _lib
+    if out is None:
+        out = torch.empty((N, k, E), dtype=torch.float32, device=dev)
+    if out_global is None:
+        out_global = torch.empty((N, E), dtype=torch.float32, device=dev)
+    row_stride = int(out.stride(1))
+    env_stride = int(out.stride(0)) if N > 1 else (k - 1) * row_stride + E
+    ws = w._struct()
+    _lib.check(lib.irbpp_order_embed(C.byref(ws), _p(state), int(state.stride(0)) if N > 1 else int(state.shape[1]), _p(sf),
+                                     int(sf.stride(0)), k, N, _p(w._base(N)), _p(out), env_stride, row_stride, _p(out_global),
+                                     int(out_global.stride(0)) if N > 1 else E, _stream(dev)), "irbpp_order_embed")
+    return out, out_global
+
+
+@torch.no_grad()
+def order_network_greedy_action(state: torch.Tensor, points: ShapePoints, indices: torch.Tensor, shape_weights: ShapeEncoderWeights,
+                                order_weights: OrderEmbedWeights, stream_weights: StreamWeights, support: torch.Tensor, *,
+                                q_out: Optional[torch.Tensor] = None, use_hip: Optional[bool] = None) -> torch.Tensor:
+    """The order network's Agent.act from the observation (``orderDQN.act(orderState, None)``, trainer.py:266, with all of
+    DQNBPP.forward for bufferSize > 1): ``state`` [N, k + L^2] -> int64[N] in [0, k), the three stages chained with no torch
+    layer in between: shape_features on the N k ids ``state[:, :k]`` (one small strided copy makes them contiguous), order_embed,
+    streams_greedy_action without a mask.  ``indices``, ``q_out`` and ``use_hip`` as in network_greedy_action (``True``: the
+    whole forward in the defined float32 arithmetic, bit for bit what the CPU form gives: on CPU tensors the head is a numpy
+    emulation of irbpp_dueling_act, not streams_greedy_action's torch lines)."""
+    k = _order_slots(state, order_weights)
+    sf = shape_features(state[:, :k].contiguous(), points, indices, shape_weights, use_hip=use_hip)
+    x, xg = order_embed(state, sf, order_weights, use_hip=use_hip)
+    if x.is_cuda:
+        return streams_greedy_action(x, xg, stream_weights, support, None, q_out=q_out, use_hip=use_hip)
+    # the CPU form stays in the defined arithmetic to the end (streams_greedy_action's CPU form ends in torch's softmax)
+    v, a = streams_logits(x, xg, stream_weights, use_hip=False)
+    _q_out_arg(q_out, int(x.shape[0]), k, x.device, "state")
+    return _dueling_act_cpu(v, a, support, q_out)
+
+
+def _dueling_act_cpu(v: torch.Tensor, a: torch.Tensor, support: torch.Tensor, q_out: Optional[torch.Tensor]) -> torch.Tensor:
+    """irbpp_dueling_act's arithmetic (csrc/irbpp_dueling.hip) without a mask, in numpy: x = (v + a) - dueling_mean(a), the
+    softmax over the atoms with dueling_dexp and a left-to-right denominator, q = ((p0 z0 + p1 z1) + p2 z2) + .., the first
+    maximum wins."""
+    import numpy as np
+    v, a, z = (t.detach().to(torch.float32).cpu().numpy() for t in (v, a, support))
+    xs = (v[:, None, :] + a) - _mean_rows_np(a)[:, None, :]
+    e = _dexp_np(xs - xs.max(-1, keepdims=True))
+    den = e[..., 0]
+    for j in range(1, e.shape[-1]):
+        den = den + e[..., j]
+    p = e / den[..., None]
+    q = p[..., 0] * z[0]
+    for j in range(1, p.shape[-1]):
+        q = q + p[..., j] * z[j]
+    if q_out is not None:
+        q_out.copy_(torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)))
+    return torch.from_numpy(q.argmax(1).astype(np.int64))
+
+
 def actor_step(envs, policy, memory: VectorReplayMemory, state: torch.Tensor, reward_clip: float = 0.0):
     """One iteration of the trainer's acting loop (trainer.py:160-186) without per-env Python:
     mask -> policy -> envs.step -> clip -> append.  ``envs`` is a GpuPackingEnv (device-tensor
