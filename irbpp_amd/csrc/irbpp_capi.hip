@@ -1287,16 +1287,33 @@ int irbpp_shape_features(const float* points_dev, int32_t n_shapes, int32_t n_po
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
 }
 
+// the heightmap encoder's part of irbpp_embed_weights and of irbpp_order_embed_weights is outside its limits: one of its six
+// arrays missing, map_len, c1, c2 or c3 out of range, or a slope that is not >= 0 (a NaN among them: read from the bits, since
+// the library is built with -fno-honor-nans, under which a comparison inside a function need not reject a NaN)
+extern "C++" {
+template <typename W>
+static bool front_encoder_bad(const W* w) {
+    uint32_t slope_bits;
+    memcpy(&slope_bits, &w->slope, 4);
+    return !w->w_conv1 || !w->b_conv1 || !w->w_conv2 || !w->b_conv2 || !w->w_conv3 || !w->b_conv3 || w->map_len < 8 ||
+           w->map_len > EMBED_MAX_MAP || w->map_len % 4 != 0 || w->c1 < 1 || w->c1 > EMBED_MAX_C1 || w->c2 < 1 ||
+           w->c2 > EMBED_MAX_C2 || w->c3 < 1 || w->c3 > EMBED_MAX_C3 || (slope_bits > 0x7f800000u && slope_bits != 0x80000000u);
+}
+}  // extern "C++"
+
+// a rows kernel may be launched with `bytes` of dynamic LDS: above 64 KB the limit has to be raised first
+static bool front_rows_lds(const void* kernel, size_t bytes) {
+    return bytes <= 64 * 1024 || hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+}
+
 int irbpp_embed(const irbpp_embed_weights* w, const float* obs_dev, int64_t obs_stride, const float* shape_feat_dev,
                 int64_t feat_stride, int32_t s_rows, int32_t n_env, float* base_dev, float* x_dev, int64_t env_stride,
                 int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream) {
-    if (!w || !w->w_conv1 || !w->b_conv1 || !w->w_conv2 || !w->b_conv2 || !w->w_conv3 || !w->b_conv3 || !w->w_c1 || !w->b_c1 ||
-        !w->w_c2 || !w->b_c2 || !w->w_p1 || !w->b_p1 || !w->w_p2 || !w->b_p2 || !obs_dev || !shape_feat_dev || !base_dev ||
-        !x_dev || !xg_dev || w->map_len < 8 || w->map_len > EMBED_MAX_MAP || w->map_len % 4 != 0 || w->c1 < 1 ||
-        w->c1 > EMBED_MAX_C1 || w->c2 < 1 || w->c2 > EMBED_MAX_C2 || w->c3 < 1 || w->c3 > EMBED_MAX_C3 || w->feat < 1 ||
-        w->feat > EMBED_MAX_WIDTH || w->cand_embed < 1 || w->cand_embed > EMBED_MAX_WIDTH || w->proj_hidden < 1 ||
-        w->proj_hidden > EMBED_MAX_WIDTH || w->embed < 1 || w->embed > EMBED_MAX_WIDTH || w->cand_hidden < 1 ||
-        w->cand_hidden > EMBED_MAX_CAND_HIDDEN || !(w->slope >= 0.0f) || s_rows < 1 || s_rows > HEAD_MAX_ROWS || n_env < 1 ||
+    if (!w || front_encoder_bad(w) || !w->w_c1 || !w->b_c1 || !w->w_c2 || !w->b_c2 || !w->w_p1 || !w->b_p1 || !w->w_p2 ||
+        !w->b_p2 || !obs_dev || !shape_feat_dev || !base_dev || !x_dev || !xg_dev || w->feat < 1 || w->feat > EMBED_MAX_WIDTH ||
+        w->cand_embed < 1 || w->cand_embed > EMBED_MAX_WIDTH || w->proj_hidden < 1 || w->proj_hidden > EMBED_MAX_WIDTH ||
+        w->embed < 1 || w->embed > EMBED_MAX_WIDTH || w->cand_hidden < 1 || w->cand_hidden > EMBED_MAX_CAND_HIDDEN || s_rows < 1 ||
+        s_rows > HEAD_MAX_ROWS || n_env < 1 ||
         obs_stride < (int64_t)5 * s_rows + 9 + (int64_t)w->map_len * w->map_len || feat_stride < w->feat || row_stride < w->embed ||
         env_stride < (int64_t)(s_rows - 1) * row_stride + w->embed || xg_stride < w->embed)
         return IRBPP_ERR_ARG;
@@ -1308,9 +1325,7 @@ int irbpp_embed(const irbpp_embed_weights* w, const float* obs_dev, int64_t obs_
                        w->w_conv2, w->b_conv2, w->w_conv3, w->b_conv3, w->w_p1, w->b_p1, obs_dev, shape_feat_dev, base_dev, g);
     if (hipGetLastError() != hipSuccess) return IRBPP_ERR_HIP;
     const size_t lds = (size_t)embed_rows_lds_floats(w->cand_hidden, w->cand_embed, w->proj_hidden, w->embed) * sizeof(float);
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)irbpp_embed_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds) != hipSuccess)
-        return IRBPP_ERR_HIP;
+    if (!front_rows_lds((const void*)irbpp_embed_rows_kernel, lds)) return IRBPP_ERR_HIP;
     hipLaunchKernelGGL(irbpp_embed_rows_kernel, dim3(n_env), dim3(EMBED_ROW_THREADS), lds, (hipStream_t)stream, w->w_c1, w->b_c1,
                        w->w_c2, w->b_c2, w->w_p1, w->w_p2, w->b_p2, obs_dev, (const float*)base_dev, x_dev, xg_dev, g);
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
@@ -1319,13 +1334,10 @@ int irbpp_embed(const irbpp_embed_weights* w, const float* obs_dev, int64_t obs_
 int irbpp_order_embed(const irbpp_order_embed_weights* w, const float* obs_dev, int64_t obs_stride, const float* shape_feat_dev,
                       int64_t feat_stride, int32_t k_slots, int32_t n_env, float* base_dev, float* x_dev, int64_t env_stride,
                       int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream) {
-    if (!w || !w->w_conv1 || !w->b_conv1 || !w->w_conv2 || !w->b_conv2 || !w->w_conv3 || !w->b_conv3 || !w->w_g1 || !w->b_g1 ||
-        !w->w_g2 || !w->b_g2 || !w->w_q || !w->w_k || !w->w_v || !w->w_o || !w->b_o || !w->w_f1 || !w->b_f1 || !w->w_f2 ||
-        !w->b_f2 || !obs_dev || !shape_feat_dev || !base_dev || !x_dev || !xg_dev || w->map_len < 8 ||
-        w->map_len > EMBED_MAX_MAP || w->map_len % 4 != 0 || w->c1 < 1 || w->c1 > EMBED_MAX_C1 || w->c2 < 1 ||
-        w->c2 > EMBED_MAX_C2 || w->c3 < 1 || w->c3 > EMBED_MAX_C3 || w->feat < 1 || w->feat > ORDER_MAX_WIDTH ||
-        w->proj_hidden < 1 || w->proj_hidden > ORDER_MAX_WIDTH || w->embed < 1 || w->embed > ORDER_MAX_WIDTH ||
-        w->ff_hidden < 1 || w->ff_hidden > ORDER_MAX_WIDTH || !(w->slope >= 0.0f) || k_slots < 2 || k_slots > ORDER_MAX_SLOTS ||
+    if (!w || front_encoder_bad(w) || !w->w_g1 || !w->b_g1 || !w->w_g2 || !w->b_g2 || !w->w_q || !w->w_k || !w->w_v || !w->w_o ||
+        !w->b_o || !w->w_f1 || !w->b_f1 || !w->w_f2 || !w->b_f2 || !obs_dev || !shape_feat_dev || !base_dev || !x_dev || !xg_dev ||
+        w->feat < 1 || w->feat > ORDER_MAX_WIDTH || w->proj_hidden < 1 || w->proj_hidden > ORDER_MAX_WIDTH || w->embed < 1 ||
+        w->embed > ORDER_MAX_WIDTH || w->ff_hidden < 1 || w->ff_hidden > ORDER_MAX_WIDTH || k_slots < 2 || k_slots > ORDER_MAX_SLOTS ||
         n_env < 1 || obs_stride < (int64_t)k_slots + (int64_t)w->map_len * w->map_len || feat_stride < w->feat ||
         row_stride < w->embed || env_stride < (int64_t)(k_slots - 1) * row_stride + w->embed || xg_stride < w->embed)
         return IRBPP_ERR_ARG;
@@ -1338,9 +1350,7 @@ int irbpp_order_embed(const irbpp_order_embed_weights* w, const float* obs_dev, 
                        w->w_conv2, w->b_conv2, w->w_conv3, w->b_conv3, w->w_g1, w->b_g1, obs_dev, base_dev, g);
     if (hipGetLastError() != hipSuccess) return IRBPP_ERR_HIP;
     const size_t lds = (size_t)order_rows_lds_floats(w->feat, w->proj_hidden, w->embed, w->ff_hidden, k_slots) * sizeof(float);
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)irbpp_order_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds) != hipSuccess)
-        return IRBPP_ERR_HIP;
+    if (!front_rows_lds((const void*)irbpp_order_rows_kernel, lds)) return IRBPP_ERR_HIP;
     hipLaunchKernelGGL(irbpp_order_rows_kernel, dim3(order_tiles(n_env, k_slots)), dim3(EMBED_ROW_THREADS), lds, (hipStream_t)stream,
                        w->w_g1, w->w_g2, w->b_g2, w->w_q, w->w_k, w->w_v, w->w_o, w->b_o, w->w_f1, w->b_f1, w->w_f2, w->b_f2,
                        shape_feat_dev, (const float*)base_dev, x_dev, xg_dev, g);

@@ -22,14 +22,14 @@
 // read whatever the values.
 //
 // Layout.  irbpp_embed_bin_kernel, one workgroup of EMBED_BIN_THREADS per bin: the heightmap goes to a zero-padded LDS tile,
-// the three convolutions pass through zero-padded LDS tiles (one output per thread and trip), thread j then runs base[j].
+// the three convolutions pass through zero-padded LDS tiles (embed_height_map, irbpp_front.h), thread j then runs base[j].
 // irbpp_embed_rows_kernel, one workgroup of EMBED_ROW_THREADS per bin, walks the bin's tiles of 64 rows in order, lane = row:
 // a layer's inputs lie in LDS as [k][row] (conflict-free dword reads), the waves own blocks of EMBED_FBLOCK output features
 // whose weights are wave-uniform __restrict__ loads (scalar cache, SGPR operands of the FMA), EMBED_KBLOCK contiguous
-// elements per feature at a time, as irbpp_shapefeat.hip does.  e1 shares the LDS of h (dead before h is written), the x tile
+// elements per feature at a time (embed_chain, irbpp_front.h).  e1 shares the LDS of h (dead before h is written), the x tile
 // (pitch 65, read transposed for coalesced stores) that of e2.  A row past S in the last tile recomputes row S-1 and is
 // dropped.  The 16 running parts of the mean stay in LDS across the tiles; x is written once and never read back.
-#include "irbpp_head.h"
+#include "irbpp_front.h"
 
 // NaNs are part of this definition (an invalid row may hold any candidate), whatever the build's command line says
 #pragma float_control(push)
@@ -40,15 +40,6 @@ namespace irbpp {
 
 constexpr int EMBED_MAX_WIDTH = 256;                     // F, Ec, P, E
 constexpr int EMBED_MAX_CAND_HIDDEN = 64;                // Hc
-constexpr int EMBED_MAX_MAP = 32;                        // L
-constexpr int EMBED_MAX_C1 = 16, EMBED_MAX_C2 = 32, EMBED_MAX_C3 = 4;
-constexpr int EMBED_BIN_THREADS = 256;
-constexpr int EMBED_ROW_THREADS = 512;
-constexpr int EMBED_ROW_WAVES = EMBED_ROW_THREADS / 64;
-constexpr int EMBED_FBLOCK = 16;                         // output features per wave and block
-constexpr int EMBED_KBLOCK = 16;                         // inputs per block: 16 contiguous weights per feature
-constexpr int EMBED_TILE_ROWS = 64;
-constexpr int EMBED_X_PITCH = EMBED_TILE_ROWS + 1;       // the x tile is read transposed
 
 struct EmbedArgs {
     long long obs_stride, feat_stride, env_stride, row_stride, xg_stride;
@@ -68,66 +59,17 @@ constexpr int embed_rows_lds_floats(int cand_hidden, int cand_embed, int proj_hi
     return embed_region_a(cand_embed, embed) + embed_region_b(cand_hidden, proj_hidden) + DUELING_PARTS * embed;
 }
 
-__device__ __forceinline__ float embed_leaky(float s, float slope) { return s > 0.0f ? s : slope * s; }
-
-// v is the same in every lane of the wave: tell the compiler so
-__device__ __forceinline__ int embed_wave_uniform(int v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_readfirstlane(v);
-#else
-    return v;
-#endif
-}
-
-// One convolution by the workgroup: src [cin][sp][sp] a zero-padded LDS tile (sp = stride * n_out + ksize - stride), out element
-// (c, y, x) = leaky(the chain from b[c] over (ci, ky, kx) ascending) -> dst[c * dst_plane + (y + dst_pad) * dst_pitch + x + dst_pad].
-template <int KSIZE, int STRIDE>
-__device__ __forceinline__ void embed_conv(const float* src, int cin, int sp, const float* __restrict__ w, const float* __restrict__ b,
-                                           int cout, int n_out, float slope, float* dst, int dst_plane, int dst_pitch, int dst_pad) {
-    const int plane = n_out * n_out;
-    for (int o = threadIdx.x; o < cout * plane; o += EMBED_BIN_THREADS) {
-        const int c = o / plane, rem = o - c * plane, y = rem / n_out, x = rem - y * n_out;
-        const float* wr = w + (size_t)c * cin * KSIZE * KSIZE;
-        const float* sr = src + (STRIDE * y) * sp + STRIDE * x;
-        float acc = b[c];
-        for (int ci = 0; ci < cin; ++ci) {
-#pragma unroll
-            for (int ky = 0; ky < KSIZE; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < KSIZE; ++kx)
-                    acc = fmaf(sr[(ci * sp + ky) * sp + kx], wr[(ci * KSIZE + ky) * KSIZE + kx], acc);
-        }
-        dst[c * dst_plane + (y + dst_pad) * dst_pitch + x + dst_pad] = embed_leaky(acc, slope);
-    }
-}
-
 // Workgroup n: base[n][0 .. P)
 extern "C" __global__ void __launch_bounds__(EMBED_BIN_THREADS)
 irbpp_embed_bin_kernel(const float* __restrict__ w_conv1, const float* __restrict__ b_conv1, const float* __restrict__ w_conv2,
                        const float* __restrict__ b_conv2, const float* __restrict__ w_conv3, const float* __restrict__ b_conv3,
                        const float* __restrict__ w_p1, const float* __restrict__ b_p1, const float* __restrict__ obs,
                        const float* __restrict__ shape_feat, float* __restrict__ base, EmbedArgs g) {
-    __shared__ float hm[(EMBED_MAX_MAP + 2) * (EMBED_MAX_MAP + 2)];
-    __shared__ float a1[EMBED_MAX_C1 * (EMBED_MAX_MAP / 2 + 2) * (EMBED_MAX_MAP / 2 + 2)];
-    __shared__ float a2[EMBED_MAX_C2 * (EMBED_MAX_MAP / 4 + 2) * (EMBED_MAX_MAP / 4 + 2)];
-    __shared__ float map[EMBED_MAX_C3 * (EMBED_MAX_MAP / 4) * (EMBED_MAX_MAP / 4)];
     const int tid = threadIdx.x;
     const size_t n = blockIdx.x;
-    const int L = g.map_len, L2 = L / 2, L4 = L / 4, p0 = L + 2, p1 = L2 + 2, p2 = L4 + 2;
     const float* height = obs + n * g.obs_stride + 5 * g.s_rows + 9;
-    for (int i = tid; i < p0 * p0; i += EMBED_BIN_THREADS) {
-        const int y = i / p0 - 1, x = i - (y + 1) * p0 - 1;
-        hm[i] = ((unsigned)y < (unsigned)L && (unsigned)x < (unsigned)L) ? height[y * L + x] : 0.0f;
-    }
-    for (int i = tid; i < g.c1 * p1 * p1; i += EMBED_BIN_THREADS) a1[i] = 0.0f;
-    for (int i = tid; i < g.c2 * p2 * p2; i += EMBED_BIN_THREADS) a2[i] = 0.0f;
-    __syncthreads();
-    embed_conv<4, 2>(hm, 1, p0, w_conv1, b_conv1, g.c1, L2, g.slope, a1, p1 * p1, p1, 1);
-    __syncthreads();
-    embed_conv<4, 2>(a1, g.c1, p1, w_conv2, b_conv2, g.c2, L4, g.slope, a2, p2 * p2, p2, 1);
-    __syncthreads();
-    embed_conv<3, 1>(a2, g.c2, p2, w_conv3, b_conv3, g.c3, L4, g.slope, map, L4 * L4, L4, 0);
-    __syncthreads();
+    const float* map = embed_height_map(height, w_conv1, b_conv1, w_conv2, b_conv2, w_conv3, b_conv3, g.map_len, g.c1, g.c2, g.c3, g.slope);
+    const int L4 = g.map_len / 4;
     const int F = g.feat, M = g.c3 * L4 * L4, ld = F + M + g.cand_embed;
     const float* sf = shape_feat + n * g.feat_stride;
     for (int j = tid; j < g.proj_hidden; j += EMBED_BIN_THREADS) {
@@ -139,37 +81,6 @@ irbpp_embed_bin_kernel(const float* __restrict__ w_conv1, const float* __restric
     }
 }
 
-// acc[m] continues its chain over the nj inputs of the block at kb (FULL: nj == EMBED_KBLOCK): xk the lane's inputs, w the
-// weights' first row, rows ld floats apart, the block's columns from w[.. + kb]
-template <bool FULL>
-__device__ __forceinline__ void embed_consume(const float (&xk)[EMBED_KBLOCK], const float* __restrict__ w, int ld, int kb, int nj, int f0,
-                                              int nf, float (&acc)[EMBED_FBLOCK]) {
-#pragma unroll
-    for (int m = 0; m < EMBED_FBLOCK; ++m) {
-        // past the wave's last feature: that feature once more, its result unused (no branch between the chains)
-        const float* wz = w + (size_t)(f0 + (m < nf ? m : nf - 1)) * ld + kb;
-#pragma unroll
-        for (int jj = 0; jj < EMBED_KBLOCK; ++jj)
-            if (FULL || jj < nj) acc[m] = fmaf(xk[jj], wz[jj], acc[m]);
-    }
-}
-
-// acc[0 .. nf) continue their chains over the K inputs in[k * 64 + lane] (LDS) against w[(f0 + m) * ld + k]
-__device__ __forceinline__ void embed_chain(const float* in, int lane, int K, const float* __restrict__ w, int ld, int f0, int nf,
-                                            float (&acc)[EMBED_FBLOCK]) {
-    for (int kb = 0; kb < K; kb += EMBED_KBLOCK) {
-        const int nj = K - kb < EMBED_KBLOCK ? K - kb : EMBED_KBLOCK;
-        float xk[EMBED_KBLOCK];
-#pragma unroll
-        for (int jj = 0; jj < EMBED_KBLOCK; ++jj)        // past the end: an input that exists, its product unused
-            xk[jj] = in[(jj < nj ? kb + jj : K - 1) * EMBED_TILE_ROWS + lane];
-        if (nj == EMBED_KBLOCK)
-            embed_consume<true>(xk, w, ld, kb, nj, f0, nf, acc);
-        else
-            embed_consume<false>(xk, w, ld, kb, nj, f0, nf, acc);
-    }
-}
-
 // Workgroup n: x[n][0 .. S)[0 .. E) and xg[n][0 .. E) from the observation row and base[n]
 extern "C" __global__ void __launch_bounds__(EMBED_ROW_THREADS)
 irbpp_embed_rows_kernel(const float* __restrict__ w_c1, const float* __restrict__ b_c1, const float* __restrict__ w_c2,
@@ -177,7 +88,7 @@ irbpp_embed_rows_kernel(const float* __restrict__ w_c1, const float* __restrict_
                         const float* __restrict__ b_p2, const float* __restrict__ obs, const float* __restrict__ base,
                         float* __restrict__ x, float* __restrict__ xg, EmbedArgs g) {
     HIP_DYNAMIC_SHARED(float, embed_tile)
-    const int tid = threadIdx.x, lane = tid & 63, wave = embed_wave_uniform(tid >> 6);
+    const int tid = threadIdx.x, lane = tid & 63, wave = front_wave_uniform(tid >> 6);
     const size_t n = blockIdx.x;
     const int S = g.s_rows, Hc = g.cand_hidden, Ec = g.cand_embed, P = g.proj_hidden, E = g.embed;
     const int ld1 = g.feat + g.c3 * (g.map_len / 4) * (g.map_len / 4) + Ec;
@@ -197,7 +108,7 @@ irbpp_embed_rows_kernel(const float* __restrict__ w_c1, const float* __restrict_
         __syncthreads();                                 // the tile before: h and the x tile have been read
         for (int i = wave; i < Hc; i += EMBED_ROW_WAVES) {
             const float* wr = w_c1 + (size_t)i * 4;
-            rb[i * EMBED_TILE_ROWS + lane] = embed_leaky(fmaf(c3, wr[3], fmaf(c2, wr[2], fmaf(c1, wr[1], fmaf(c0, wr[0], b_c1[i])))), g.slope);
+            rb[i * EMBED_TILE_ROWS + lane] = front_leaky(fmaf(c3, wr[3], fmaf(c2, wr[2], fmaf(c1, wr[1], fmaf(c0, wr[0], b_c1[i])))), g.slope);
         }
         __syncthreads();
         for (int f0 = wave * EMBED_FBLOCK; f0 < Ec; f0 += EMBED_ROW_WAVES * EMBED_FBLOCK) {
@@ -219,7 +130,7 @@ irbpp_embed_rows_kernel(const float* __restrict__ w_c1, const float* __restrict_
             embed_chain(ra, lane, Ec, w_p1c, ld1, f0, nf, acc);
 #pragma unroll
             for (int m = 0; m < EMBED_FBLOCK; ++m)
-                if (m < nf) rb[(f0 + m) * EMBED_TILE_ROWS + lane] = embed_leaky(acc[m], g.slope);
+                if (m < nf) rb[(f0 + m) * EMBED_TILE_ROWS + lane] = front_leaky(acc[m], g.slope);
         }
         __syncthreads();                                 // h is whole, e2 has been read
         for (int f0 = wave * EMBED_FBLOCK; f0 < E; f0 += EMBED_ROW_WAVES * EMBED_FBLOCK) {

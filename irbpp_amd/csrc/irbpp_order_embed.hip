@@ -9,7 +9,7 @@
 //   re-associated; lin(W, b, x)[j] starts from b[j].  leaky(s) = s > 0 ? s : slope * s, relu(s) = s > 0 ? s : +0.
 //   Observation row of bin n: obs[0 .. k) the k buffered item ids (not read here), obs[k ..] the L x L heightmap, row-major.
 //   shape_feat[n][i][0 .. F): irbpp_shape_features over the N k ids, bin-major.
-//   map[0 .. M), M = C3 (L/4)^2: the heightmap CNN as irbpp_embed.hip defines it (embed_conv).
+//   map[0 .. M), M = C3 (L/4)^2: the heightmap CNN of irbpp_embed.hip's definition (embed_height_map, irbpp_front.h).
 //   base[j]  = the chain from b_g1[j] over map[0 .. M) against W_g1[j][F .. F+M)                       per bin, j < P
 //   g[i][j]  = leaky(the chain continued from base[j] over shape_feat[i][0 .. F) against W_g1[j][0 .. F))   per slot i < k
 //   h0[i]    = lin(W_g2, b_g2, g[i])                                                                   E values
@@ -28,7 +28,7 @@
 // A function of the inputs alone: not of N, of strides or of the tiles.  No index depends on data: nothing out of range is
 // read whatever the values.  Inputs must be finite (a NaN gives unspecified values).
 //
-// Layout.  irbpp_order_bin_kernel, one workgroup of EMBED_BIN_THREADS per bin: irbpp_embed_bin_kernel's CNN through
+// Layout.  irbpp_order_bin_kernel, one workgroup of EMBED_BIN_THREADS per bin: irbpp_front.h's heightmap encoder through
 // zero-padded LDS tiles, thread j then runs base[j].  irbpp_order_rows_kernel, one workgroup of EMBED_ROW_THREADS per tile
 // of 64 rows: a row is a (bin, slot) pair taken bin-major, a tile holds 64 / k whole bins (attention never crosses a
 // tile), lane = row; a lane past the tile's last row recomputes that last row and is dropped.  A layer's inputs lie in LDS as
@@ -40,7 +40,7 @@
 // computed them (the same thread owns the same features of the residual's other term).  The compatibility chains run over
 // all E features in order: with E > ORDER_QK_BLOCK the Q and K blocks are produced and consumed in turn, the running chains
 // in registers (row = lane, key slot = wave, wave + 8, ..).  The softmax of a row is its lane's of wave 0.
-#include "irbpp_head.h"
+#include "irbpp_front.h"
 
 #pragma float_control(push)
 #pragma float_control(precise, on)
@@ -48,7 +48,7 @@
 
 namespace irbpp {
 
-constexpr int ORDER_MAX_WIDTH = EMBED_MAX_WIDTH;         // F, P, E, Hf
+constexpr int ORDER_MAX_WIDTH = 256;                     // F, P, E, Hf
 constexpr int ORDER_MAX_SLOTS = EMBED_TILE_ROWS;         // k: a bin fits a tile
 constexpr int ORDER_QK_BLOCK = EMBED_ROW_WAVES * EMBED_FBLOCK;   // features of Q and of K in LDS at a time: one block per wave
 constexpr int ORDER_PASSES = ORDER_MAX_WIDTH / ORDER_QK_BLOCK;   // blocks of E output features per wave
@@ -82,27 +82,11 @@ irbpp_order_bin_kernel(const float* __restrict__ w_conv1, const float* __restric
                        const float* __restrict__ b_conv2, const float* __restrict__ w_conv3, const float* __restrict__ b_conv3,
                        const float* __restrict__ w_g1, const float* __restrict__ b_g1, const float* __restrict__ obs,
                        float* __restrict__ base, OrderEmbedArgs g) {
-    __shared__ float hm[(EMBED_MAX_MAP + 2) * (EMBED_MAX_MAP + 2)];
-    __shared__ float a1[EMBED_MAX_C1 * (EMBED_MAX_MAP / 2 + 2) * (EMBED_MAX_MAP / 2 + 2)];
-    __shared__ float a2[EMBED_MAX_C2 * (EMBED_MAX_MAP / 4 + 2) * (EMBED_MAX_MAP / 4 + 2)];
-    __shared__ float map[EMBED_MAX_C3 * (EMBED_MAX_MAP / 4) * (EMBED_MAX_MAP / 4)];
     const int tid = threadIdx.x;
     const size_t n = blockIdx.x;
-    const int L = g.map_len, L2 = L / 2, L4 = L / 4, p0 = L + 2, p1 = L2 + 2, p2 = L4 + 2;
     const float* height = obs + n * g.obs_stride + g.k_slots;
-    for (int i = tid; i < p0 * p0; i += EMBED_BIN_THREADS) {
-        const int y = i / p0 - 1, x = i - (y + 1) * p0 - 1;
-        hm[i] = ((unsigned)y < (unsigned)L && (unsigned)x < (unsigned)L) ? height[y * L + x] : 0.0f;
-    }
-    for (int i = tid; i < g.c1 * p1 * p1; i += EMBED_BIN_THREADS) a1[i] = 0.0f;
-    for (int i = tid; i < g.c2 * p2 * p2; i += EMBED_BIN_THREADS) a2[i] = 0.0f;
-    __syncthreads();
-    embed_conv<4, 2>(hm, 1, p0, w_conv1, b_conv1, g.c1, L2, g.slope, a1, p1 * p1, p1, 1);
-    __syncthreads();
-    embed_conv<4, 2>(a1, g.c1, p1, w_conv2, b_conv2, g.c2, L4, g.slope, a2, p2 * p2, p2, 1);
-    __syncthreads();
-    embed_conv<3, 1>(a2, g.c2, p2, w_conv3, b_conv3, g.c3, L4, g.slope, map, L4 * L4, L4, 0);
-    __syncthreads();
+    const float* map = embed_height_map(height, w_conv1, b_conv1, w_conv2, b_conv2, w_conv3, b_conv3, g.map_len, g.c1, g.c2, g.c3, g.slope);
+    const int L4 = g.map_len / 4;
     const int F = g.feat, M = g.c3 * L4 * L4, ld = F + M;
     for (int j = tid; j < g.proj_hidden; j += EMBED_BIN_THREADS) {
         const float* wr = w_g1 + (size_t)j * ld + F;
@@ -126,7 +110,7 @@ irbpp_order_rows_kernel(const float* __restrict__ w_g1, const float* __restrict_
                         const float* __restrict__ shape_feat, const float* __restrict__ base, float* __restrict__ x,
                         float* __restrict__ xg, OrderEmbedArgs g) {
     HIP_DYNAMIC_SHARED(float, order_tile)
-    const int tid = threadIdx.x, lane = tid & 63, wave = embed_wave_uniform(tid >> 6);
+    const int tid = threadIdx.x, lane = tid & 63, wave = front_wave_uniform(tid >> 6);
     const int k = g.k_slots, F = g.feat, P = g.proj_hidden, E = g.embed, Hf = g.ff_hidden;
     const int ld1 = F + g.c3 * (g.map_len / 4) * (g.map_len / 4);
     const int per_tile = order_tile_bins(k);
@@ -154,7 +138,7 @@ irbpp_order_rows_kernel(const float* __restrict__ w_g1, const float* __restrict_
             embed_chain(ra, lane, F, w_g1, ld1, f0, nf, acc);
 #pragma unroll
             for (int m = 0; m < EMBED_FBLOCK; ++m)
-                if (m < nf) rb[(f0 + m) * EMBED_TILE_ROWS + lane] = embed_leaky(acc[m], g.slope);
+                if (m < nf) rb[(f0 + m) * EMBED_TILE_ROWS + lane] = front_leaky(acc[m], g.slope);
         }
     }
     __syncthreads();                                     // g is whole, the shape features have been read

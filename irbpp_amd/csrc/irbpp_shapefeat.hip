@@ -24,7 +24,7 @@
 // and consumed at once by the wave's accumulators in ascending i, as irbpp_streams.hip does; per trip the wave reduces each
 // feature's keys once (lane m keeps feature m's running maximum).  A lane without a point brings the key 0, which no value
 // has.  irbpp_shape_gather_kernel: out[m][f] = max_c partial[ids[m]][c][f].
-#include "irbpp_head.h"
+#include "irbpp_front.h"
 
 // NaNs are part of this definition, whatever the build's command line says about them elsewhere
 #pragma float_control(push)
@@ -70,17 +70,6 @@ __device__ __forceinline__ uint32_t shape_key_bits(uint32_t key) {       // the 
     return (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
 }
 
-__device__ __forceinline__ float shape_leaky(float s, float slope) { return s > 0.0f ? s : slope * s; }
-
-// v is the same in every lane of the wave: tell the compiler so
-__device__ __forceinline__ int shape_wave_uniform(int v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_readfirstlane(v);
-#else
-    return v;
-#endif
-}
-
 // ids[m] as a shape index, -1 for one outside [0, n_shapes)
 __device__ __forceinline__ int shape_id(const void* __restrict__ ids, int ids_are_float, long long ids_stride, long long m,
                                         int n_shapes) {
@@ -98,21 +87,6 @@ struct ShapeArgs {
     float slope;
 };
 
-// acc[m] continues its chain over the nj hidden units of the block at ib (FULL: nj == SHAPE_HBLOCK)
-template <bool FULL>
-__device__ __forceinline__ void shape_consume(const float (&h)[SHAPE_HBLOCK], const float* __restrict__ w2, int H1, int ib, int nj,
-                                              int f0, int nf, float (&acc)[SHAPE_FBLOCK]) {
-#pragma unroll
-    for (int m = 0; m < SHAPE_FBLOCK; ++m) {
-        // past the wave's last feature: that feature once more, its result unused (no branch between the chains, so that
-        // the compiler may interleave them and batch the weight loads)
-        const float* wz = w2 + (size_t)(f0 + (m < nf ? m : nf - 1)) * H1 + ib;
-#pragma unroll
-        for (int jj = 0; jj < SHAPE_HBLOCK; ++jj)
-            if (FULL || jj < nj) acc[m] = fmaf(h[jj], wz[jj], acc[m]);
-    }
-}
-
 // one point -> acc[0 .. nf): s[f0 + m] before the second leaky
 __device__ __forceinline__ void shape_point(float p0, float p1, float p2, const float* __restrict__ w1, const float* __restrict__ b1,
                                             const float* __restrict__ w2, const float* __restrict__ b2, int H1, float slope, int f0,
@@ -126,12 +100,12 @@ __device__ __forceinline__ void shape_point(float p0, float p1, float p2, const 
         for (int jj = 0; jj < SHAPE_HBLOCK; ++jj) {
             const int i = jj < nj ? ib + jj : H1 - 1;        // past the end: a unit that exists, its result unused
             const float* wr = w1 + (size_t)i * 3;
-            h[jj] = shape_leaky(fmaf(p2, wr[2], fmaf(p1, wr[1], fmaf(p0, wr[0], b1[i]))), slope);
+            h[jj] = front_leaky(fmaf(p2, wr[2], fmaf(p1, wr[1], fmaf(p0, wr[0], b1[i]))), slope);
         }
         if (nj == SHAPE_HBLOCK)
-            shape_consume<true>(h, w2, H1, ib, nj, f0, nf, acc);
+            front_consume<SHAPE_FBLOCK, SHAPE_HBLOCK, true>(h, w2, H1, ib, nj, f0, nf, acc);
         else
-            shape_consume<false>(h, w2, H1, ib, nj, f0, nf, acc);
+            front_consume<SHAPE_FBLOCK, SHAPE_HBLOCK, false>(h, w2, H1, ib, nj, f0, nf, acc);
     }
 }
 
@@ -152,7 +126,7 @@ irbpp_shape_partial_kernel(const float* __restrict__ points, const int32_t* __re
     for (int w = 0; w < threads / 64; ++w) mine |= occurs[w];
     if (!mine) return;                                   // the whole workgroup
 
-    const int f0 = shape_wave_uniform(tid >> 6) * SHAPE_FBLOCK;         // in SGPRs: the weights' addresses are scalar
+    const int f0 = front_wave_uniform(tid >> 6) * SHAPE_FBLOCK;         // in SGPRs: the weights' addresses are scalar
     const int nf = g.feat - f0 < SHAPE_FBLOCK ? g.feat - f0 : SHAPE_FBLOCK;
     const int j0 = c * g.chunk_points;
     const int j1 = j0 + g.chunk_points < g.k ? j0 + g.chunk_points : g.k;
@@ -192,7 +166,7 @@ irbpp_shape_partial_kernel(const float* __restrict__ points, const int32_t* __re
         const uint32_t bits = shape_key_bits(mine_key);
         float s;
         memcpy(&s, &bits, 4);
-        const uint32_t out_bits = shape_key_bits(shape_key(shape_leaky(s, g.slope)));
+        const uint32_t out_bits = shape_key_bits(shape_key(front_leaky(s, g.slope)));
         memcpy(&partial[((size_t)u * g.chunks + c) * g.feat + f0 + lane], &out_bits, 4);
     }
 }

@@ -1222,7 +1222,65 @@ class _IrbppEmbedWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in _EMBED_FIELDS] + [(n, C.c_int32) for n in _EMBED_SIZES] + [("slope", C.c_float)]
 
 
-class EmbedWeights(object):
+class _FrontWeights(object):
+    """What EmbedWeights and OrderEmbedWeights share: the heightmap encoder's three Conv2d with their checks, and what follows
+    from a subclass's ``_NAME`` (the prefix of its messages), ``_FIELDS`` (the tensors, in ``layers``' order, a bias after its
+    weight), ``_SIZES``, ``_STRUCT`` (the C struct of the three), ``_MAX`` (the limits of the widths, ``_MAX_WIDTH`` where it
+    names none) and ``_LIMITS`` (what the limits' message says after the prefix)."""
+    _MAX = {}
+
+    @staticmethod
+    def _weighted(modules, dim: int) -> list:
+        """The members with a weight of ``dim`` dimensions, in order: the activations between them are skipped."""
+        return [m for m in modules if getattr(m, "weight", None) is not None and m.weight.dim() == dim]
+
+    def _encoder(self, convs, negative_slope: float, map_len: int) -> None:
+        """slope, map_len, c1, c2, c3 and map_feat from the three Conv2d and the heightmap's side."""
+        self.slope, self.map_len = float(negative_slope), int(map_len)
+        for m, (k, s, p) in zip(convs, ((4, 2, 1), (4, 2, 1), (3, 1, 1))):
+            if tuple(m.weight.shape[2:]) != (k, k) or tuple(getattr(m, "stride", (s, s))) != (s, s) or \
+                    tuple(getattr(m, "padding", (p, p))) != (p, p):
+                raise ValueError(f"{self._NAME}: Conv2d(1, c1, 4, 2, 1), Conv2d(c1, c2, 4, 2, 1), Conv2d(c2, c3, 3, 1, 1)")
+        self.c1, self.c2, self.c3 = (int(m.weight.shape[0]) for m in convs)
+        if self.map_len % 4 != 0 or not 8 <= self.map_len <= 32:
+            raise ValueError(f"{self._NAME}: map_len is a multiple of 4 in [8, 32]")
+        self.map_feat = self.c3 * (self.map_len // 4) ** 2
+
+    def _finish(self, want) -> None:
+        """``layers`` against the shapes ``want``, the limits, and the first copy."""
+        for m, shape in zip(self.layers, want):
+            if tuple(m.weight.shape) != shape or (m.bias is not None and tuple(m.bias.shape) != shape[:1]):
+                raise ValueError(f"{self._NAME}: a weight of shape {tuple(m.weight.shape)} beside the expected {shape}")
+        if not (1 <= self.c1 <= 16 and 1 <= self.c2 <= 32 and 1 <= self.c3 <= 4 and self.slope >= 0 and
+                all(1 <= getattr(self, n) <= self._MAX.get(n, self._MAX_WIDTH) for n in self._SIZES[4:])):
+            raise ValueError(f"{self._NAME}: 1 <= c1 <= 16, 1 <= c2 <= 32, 1 <= c3 <= 4, {self._LIMITS} and negative_slope >= 0")
+        self.device = self.layers[0].weight.device
+        self._workspace = {}
+        self.refresh()
+
+    @classmethod
+    def from_layers(cls, *args, **kw):
+        return cls(*args, **kw)
+
+    @torch.no_grad()
+    def refresh(self):
+        names = iter(self._FIELDS)
+        for m in self.layers:
+            setattr(self, next(names), _f32(m.weight.detach(), self.device).clone())
+            if m.bias is not None:
+                setattr(self, next(names), _f32(m.bias.detach(), self.device).clone())
+        return self
+
+    def _struct(self):
+        return self._STRUCT(*(getattr(self, n).data_ptr() for n in self._FIELDS), *(getattr(self, n) for n in self._SIZES), self.slope)
+
+    def _base(self, n_env: int) -> torch.Tensor:
+        if n_env not in self._workspace:
+            self._workspace = {n_env: torch.empty((n_env, self.proj_hidden), dtype=torch.float32, device=self.device)}
+        return self._workspace[n_env]
+
+
+class EmbedWeights(_FrontWeights):
     """The layers of DQNBPP's embedding stage as float32 contiguous tensors in torch's layouts: ``heightEncoder``'s three
     Conv2d (4x4 stride 2 pad 1, 4x4 stride 2 pad 1, 3x3 stride 1 pad 1), ``init_candidate_embed``'s two Linear and
     ``project_layer``'s two Linear, and the LeakyReLUs' slope: what embed multiplies by.  Takes the three ``nn.Sequential``s
@@ -1230,62 +1288,24 @@ class EmbedWeights(object):
     shapes fit each other; ``map_len`` is the heightmap's side L (the reference asserts 32), from which the shape feature's
     width follows: F = project_layer[0].in_features - c3 (L/4)^2 - cand_embed.  Copies: call ``refresh()`` after every
     optimiser step."""
+    _NAME, _FIELDS, _SIZES, _STRUCT = "embed", _EMBED_FIELDS, _EMBED_SIZES, _IrbppEmbedWeights
+    _MAX_WIDTH, _MAX = EMBED_MAX_WIDTH, {"cand_hidden": EMBED_MAX_CAND_HIDDEN}
+    _LIMITS = "1 <= cand_hidden <= 64, 1 <= feat, cand_embed, proj_hidden, embed <= 256"
 
     def __init__(self, height_encoder, init_candidate_embed, project_layer, negative_slope: float = 0.01, *, map_len: int = 32):
-        convs = [m for m in height_encoder if getattr(m, "weight", None) is not None and m.weight.dim() == 4]
-        cands = [m for m in init_candidate_embed if getattr(m, "weight", None) is not None and m.weight.dim() == 2]
-        projs = [m for m in project_layer if getattr(m, "weight", None) is not None and m.weight.dim() == 2]
+        convs, cands, projs = self._weighted(height_encoder, 4), self._weighted(init_candidate_embed, 2), self._weighted(project_layer, 2)
         if len(convs) != 3 or len(cands) != 2 or len(projs) != 2:
             raise ValueError("embed: three Conv2d, two Linear (candidates) and two Linear (project layer)")
         self.layers = tuple(convs + cands + projs)
         if any(m.bias is None for m in self.layers):
             raise ValueError("embed: every layer has a bias")
-        self.slope, self.map_len = float(negative_slope), int(map_len)
-        for m, (k, s, p) in zip(convs, ((4, 2, 1), (4, 2, 1), (3, 1, 1))):
-            if tuple(m.weight.shape[2:]) != (k, k) or tuple(getattr(m, "stride", (s, s))) != (s, s) or \
-                    tuple(getattr(m, "padding", (p, p))) != (p, p):
-                raise ValueError("embed: Conv2d(1, c1, 4, 2, 1), Conv2d(c1, c2, 4, 2, 1), Conv2d(c2, c3, 3, 1, 1)")
-        self.c1, self.c2, self.c3 = (int(m.weight.shape[0]) for m in convs)
+        self._encoder(convs, negative_slope, map_len)
         self.cand_hidden, self.cand_embed = int(cands[0].weight.shape[0]), int(cands[1].weight.shape[0])
         self.proj_hidden, self.embed = int(projs[0].weight.shape[0]), int(projs[1].weight.shape[0])
-        if self.map_len % 4 != 0 or not 8 <= self.map_len <= 32:
-            raise ValueError("embed: map_len is a multiple of 4 in [8, 32]")
-        self.map_feat = self.c3 * (self.map_len // 4) ** 2
         self.feat = int(projs[0].weight.shape[1]) - self.map_feat - self.cand_embed
-        want = [(self.c1, 1, 4, 4), (self.c2, self.c1, 4, 4), (self.c3, self.c2, 3, 3), (self.cand_hidden, 4),
-                (self.cand_embed, self.cand_hidden), (self.proj_hidden, self.feat + self.map_feat + self.cand_embed),
-                (self.embed, self.proj_hidden)]
-        for m, shape in zip(self.layers, want):
-            if tuple(m.weight.shape) != shape or tuple(m.bias.shape) != shape[:1]:
-                raise ValueError(f"embed: a weight of shape {tuple(m.weight.shape)} beside the expected {shape}")
-        if not (1 <= self.c1 <= 16 and 1 <= self.c2 <= 32 and 1 <= self.c3 <= 4 and 1 <= self.cand_hidden <= EMBED_MAX_CAND_HIDDEN and
-                all(1 <= v <= EMBED_MAX_WIDTH for v in (self.feat, self.cand_embed, self.proj_hidden, self.embed)) and self.slope >= 0):
-            raise ValueError("embed: 1 <= c1 <= 16, 1 <= c2 <= 32, 1 <= c3 <= 4, 1 <= cand_hidden <= 64, 1 <= feat, cand_embed, "
-                             "proj_hidden, embed <= 256 and negative_slope >= 0")
-        self.device = convs[0].weight.device
-        self._workspace = {}
-        self.refresh()
-
-    @classmethod
-    def from_layers(cls, height_encoder, init_candidate_embed, project_layer, negative_slope: float = 0.01, *,
-                    map_len: int = 32) -> "EmbedWeights":
-        return cls(height_encoder, init_candidate_embed, project_layer, negative_slope, map_len=map_len)
-
-    @torch.no_grad()
-    def refresh(self) -> "EmbedWeights":
-        for i, m in enumerate(self.layers):
-            setattr(self, _EMBED_FIELDS[2 * i], _f32(m.weight.detach(), self.device).clone())
-            setattr(self, _EMBED_FIELDS[2 * i + 1], _f32(m.bias.detach(), self.device).clone())
-        return self
-
-    def _struct(self) -> _IrbppEmbedWeights:
-        return _IrbppEmbedWeights(*(getattr(self, n).data_ptr() for n in _EMBED_FIELDS), *(getattr(self, n) for n in _EMBED_SIZES),
-                                  self.slope)
-
-    def _base(self, n_env: int) -> torch.Tensor:
-        if n_env not in self._workspace:
-            self._workspace = {n_env: torch.empty((n_env, self.proj_hidden), dtype=torch.float32, device=self.device)}
-        return self._workspace[n_env]
+        self._finish([(self.c1, 1, 4, 4), (self.c2, self.c1, 4, 4), (self.c3, self.c2, 3, 3), (self.cand_hidden, 4),
+                      (self.cand_embed, self.cand_hidden), (self.proj_hidden, self.feat + self.map_feat + self.cand_embed),
+                      (self.embed, self.proj_hidden)])
 
 
 def _chain_np(acc, w, x):
@@ -1322,19 +1342,34 @@ def _mean_rows_np(x):
     return total / np.float32(S)
 
 
+def _np32(t: torch.Tensor):
+    return t.detach().to(torch.float32).cpu().numpy()
+
+
+def _height_map_np(hm, w, leaky):
+    """The heightmap encoder in the defined arithmetic: hm float32 numpy [N, 1, L, L] -> map [N, M]."""
+    a = leaky(_conv_np(hm, _np32(w.w_conv1), _np32(w.b_conv1), 2, 1))
+    a = leaky(_conv_np(a, _np32(w.w_conv2), _np32(w.b_conv2), 2, 1))
+    return leaky(_conv_np(a, _np32(w.w_conv3), _np32(w.b_conv3), 1, 1)).reshape(hm.shape[0], w.map_feat)
+
+
+def _height_map_torch(hm: torch.Tensor, w) -> torch.Tensor:
+    """The heightmap encoder as torch's layers: hm [N, 1, L, L] -> map [N, M]."""
+    F = torch.nn.functional
+    a = F.leaky_relu(F.conv2d(hm, w.w_conv1, w.b_conv1, stride=2, padding=1), w.slope)
+    a = F.leaky_relu(F.conv2d(a, w.w_conv2, w.b_conv2, stride=2, padding=1), w.slope)
+    return F.leaky_relu(F.conv2d(a, w.w_conv3, w.b_conv3, stride=1, padding=1), w.slope).reshape(hm.shape[0], -1)
+
+
 def _embed_cpu(state: torch.Tensor, sf: torch.Tensor, w: EmbedWeights, S: int) -> Tuple[torch.Tensor, torch.Tensor]:
     import numpy as np
-    f32 = np.float32
-    n = lambda t: t.detach().to(torch.float32).cpu().numpy()  # noqa: E731
+    f32, n = np.float32, _np32
     leaky = lambda s: np.where(s > 0, s, f32(w.slope) * s).astype(f32)  # noqa: E731
     obs, sf = n(state), n(sf)
     N, L, F_, M = obs.shape[0], w.map_len, w.feat, w.map_feat
     with np.errstate(all="ignore"):
         rows = obs[:, :5 * S].reshape(N, S, 5)
-        hm = obs[:, 5 * S + 9:5 * S + 9 + L * L].reshape(N, 1, L, L)
-        a = leaky(_conv_np(hm, n(w.w_conv1), n(w.b_conv1), 2, 1))
-        a = leaky(_conv_np(a, n(w.w_conv2), n(w.b_conv2), 2, 1))
-        fmap = leaky(_conv_np(a, n(w.w_conv3), n(w.b_conv3), 1, 1)).reshape(N, M)
+        fmap = _height_map_np(obs[:, 5 * S + 9:5 * S + 9 + L * L].reshape(N, 1, L, L), w, leaky)
         w_p1 = n(w.w_p1)
         base = np.broadcast_to(n(w.b_p1), (N, w.proj_hidden)).astype(f32)
         base = _chain_np(_chain_np(base, w_p1[:, :F_], sf), w_p1[:, F_:F_ + M], fmap)
@@ -1350,16 +1385,50 @@ def _embed_torch(state: torch.Tensor, sf: torch.Tensor, w: EmbedWeights, S: int)
     F = torch.nn.functional
     N, L, FM = state.shape[0], w.map_len, w.feat + w.map_feat
     rows = state[:, :5 * S].reshape(N, S, 5)
-    hm = state[:, 5 * S + 9:5 * S + 9 + L * L].reshape(N, 1, L, L)
-    a = F.leaky_relu(F.conv2d(hm, w.w_conv1, w.b_conv1, stride=2, padding=1), w.slope)
-    a = F.leaky_relu(F.conv2d(a, w.w_conv2, w.b_conv2, stride=2, padding=1), w.slope)
-    fmap = F.leaky_relu(F.conv2d(a, w.w_conv3, w.b_conv3, stride=1, padding=1), w.slope).reshape(N, -1)
+    fmap = _height_map_torch(state[:, 5 * S + 9:5 * S + 9 + L * L].reshape(N, 1, L, L), w)
     base = F.linear(torch.cat((sf, fmap), 1), w.w_p1[:, :FM], w.b_p1)         # once per bin, not once per row
     e2 = F.linear(F.leaky_relu(F.linear(rows[:, :, :4], w.w_c1, w.b_c1), w.slope), w.w_c2, w.b_c2)
     h = F.leaky_relu(F.linear(e2, w.w_p1[:, FM:]).add_(base[:, None, :]), w.slope)
     x = F.linear(h, w.w_p2, w.b_p2)
     x = torch.where((rows[:, :, 4] == 1)[:, :, None], x, torch.zeros((), dtype=x.dtype, device=x.device))
     return x, x.mean(1)
+
+
+def _front_state(state: torch.Tensor, dev) -> torch.Tensor:
+    """The observation block as float32 on the weights' device, rows contiguous and apart (a slice passes as it is)."""
+    state = state.detach().to(device=dev, dtype=torch.float32)
+    if state.stride(1) != 1 or (state.shape[0] > 1 and state.stride(0) < state.shape[1]):
+        state = state.contiguous()
+    return state
+
+
+def _front_out(out: Optional[torch.Tensor], out_global: Optional[torch.Tensor], N: int, S: int, E: int, dev, allocate: bool):
+    """``out`` [N, S, E] / ``out_global`` [N, E] of embed and order_embed checked and, with ``allocate`` (the kernels' path),
+    made where missing -> (out, out_global, env_stride, row_stride, xg_stride): the strides irbpp_embed / irbpp_order_embed
+    take, None without ``allocate``.  A dimension of one element has no stride of its own: the library gets what contiguous
+    rows would have."""
+    if out is not None and (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (N, S, E) or
+                            (E > 1 and out.stride(2) != 1) or (S > 1 and out.stride(1) < E) or
+                            (N > 1 and out.stride(0) < (S - 1) * int(out.stride(1)) + E)):
+        raise ValueError(f"out must be a float32 [{N}, {S}, {E}] tensor on the weights' device with contiguous rows")
+    if out_global is not None and (out_global.dtype != torch.float32 or out_global.device != dev or
+                                   tuple(out_global.shape) != (N, E) or (E > 1 and out_global.stride(1) != 1) or
+                                   (N > 1 and out_global.stride(0) < E)):
+        raise ValueError(f"out_global must be a float32 [{N}, {E}] tensor on the weights' device with contiguous rows")
+    if not allocate:
+        return out, out_global, None, None, None
+    if out is None:
+        out = torch.empty((N, S, E), dtype=torch.float32, device=dev)
+    if out_global is None:
+        out_global = torch.empty((N, E), dtype=torch.float32, device=dev)
+    row_stride = int(out.stride(1)) if S > 1 else E
+    env_stride = int(out.stride(0)) if N > 1 else (S - 1) * row_stride + E
+    return out, out_global, env_stride, row_stride, int(out_global.stride(0)) if N > 1 else E
+
+
+def _front_copy(x: torch.Tensor, xg: torch.Tensor, out: Optional[torch.Tensor], out_global: Optional[torch.Tensor]):
+    """What a fallback computed, in ``out`` / ``out_global`` where the caller gave them."""
+    return x if out is None else out.copy_(x), xg if out_global is None else out_global.copy_(xg)
 
 
 def _embed_rows(state: torch.Tensor, w: EmbedWeights) -> int:
@@ -1391,41 +1460,21 @@ def embed(state: torch.Tensor, shape_feature: torch.Tensor, weights: EmbedWeight
     S = _embed_rows(state, w)
     N, E = int(state.shape[0]), w.embed
     dev = w.device
-    state = state.detach().to(device=dev, dtype=torch.float32)
-    if state.stride(1) != 1 or (N > 1 and state.stride(0) < state.shape[1]):
-        state = state.contiguous()
+    state = _front_state(state, dev)
     sf = shape_feature.detach().to(device=dev, dtype=torch.float32)
     if tuple(sf.shape) != (N, w.feat):
         raise ValueError(f"shape_feature must be [{N}, {w.feat}]")
     if (w.feat > 1 and sf.stride(1) != 1) or (N > 1 and sf.stride(0) < w.feat):
         sf = sf.contiguous()
-    if out is not None and (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (N, S, E) or
-                            (E > 1 and out.stride(2) != 1) or (S > 1 and out.stride(1) < E) or
-                            (N > 1 and out.stride(0) < (S - 1) * max(int(out.stride(1)), E) + E)):
-        raise ValueError(f"out must be a float32 [{N}, {S}, {E}] tensor on the weights' device with contiguous rows")
-    if out_global is not None and (out_global.dtype != torch.float32 or out_global.device != dev or
-                                   tuple(out_global.shape) != (N, E) or (E > 1 and out_global.stride(1) != 1) or
-                                   (N > 1 and out_global.stride(0) < E)):
-        raise ValueError(f"out_global must be a float32 [{N}, {E}] tensor on the weights' device with contiguous rows")
     lib = _head_lib(w.w_p1, use_hip, EMBED_HIP_DEFAULT)
+    out, out_global, env_stride, row_stride, xg_stride = _front_out(out, out_global, N, S, E, dev, lib is not None)
     if lib is None:
-        x, xg = _embed_torch(state, sf, w, S) if dev.type == "cuda" else _embed_cpu(state, sf, w, S)
-        if out is not None:
-            x = out.copy_(x)
-        if out_global is not None:
-            xg = out_global.copy_(xg)
-        return x, xg
+        return _front_copy(*(_embed_torch(state, sf, w, S) if dev.type == "cuda" else _embed_cpu(state, sf, w, S)), out, out_global)
     from . import _lib
-    if out is None:
-        out = torch.empty((N, S, E), dtype=torch.float32, device=dev)
-    if out_global is None:
-        out_global = torch.empty((N, E), dtype=torch.float32, device=dev)
-    row_stride = max(int(out.stride(1)), E) if S > 1 else E
-    env_stride = int(out.stride(0)) if N > 1 else (S - 1) * row_stride + E
     ws = w._struct()
     _lib.check(lib.irbpp_embed(C.byref(ws), _p(state), int(state.stride(0)) if N > 1 else int(state.shape[1]), _p(sf),
                                int(sf.stride(0)) if N > 1 else w.feat, S, N, _p(w._base(N)), _p(out), env_stride, row_stride,
-                               _p(out_global), int(out_global.stride(0)) if N > 1 else E, _stream(dev)), "irbpp_embed")
+                               _p(out_global), xg_stride, _stream(dev)), "irbpp_embed")
     return out, out_global
 
 
@@ -1464,7 +1513,7 @@ class _IrbppOrderEmbedWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in _ORDER_FIELDS] + [(n, C.c_int32) for n in _ORDER_SIZES] + [("slope", C.c_float)]
 
 
-class OrderEmbedWeights(object):
+class OrderEmbedWeights(_FrontWeights):
     """The layers of the order network's embedding stage (DQNBPP with bufferSize > 1) as float32 contiguous tensors in torch's
     layouts: ``heightEncoder``'s three Conv2d, ``gat_project_layer``'s two Linear and ``embedder``, a GraphAttentionEncoder of
     one layer and one head, read as ``embedder.layers[0]``: ``[0].module`` gives ``W_query``, ``W_key``, ``W_val`` (no bias)
@@ -1472,10 +1521,12 @@ class OrderEmbedWeights(object):
     layer, on an ``init_embed`` and on widths that do not line up.  ``map_len`` is the heightmap's side L, from which the
     shape feature's width follows: F = gat_project_layer[0].in_features - c3 (L/4)^2.  Copies: call ``refresh()`` after every
     optimiser step."""
+    _NAME, _FIELDS, _SIZES, _STRUCT = "order_embed", _ORDER_FIELDS, _ORDER_SIZES, _IrbppOrderEmbedWeights
+    _MAX_WIDTH = ORDER_MAX_WIDTH
+    _LIMITS = "1 <= feat, proj_hidden, embed, ff_hidden <= 256"
 
     def __init__(self, height_encoder, gat_project_layer, embedder, negative_slope: float = 0.01, *, map_len: int = 32):
-        convs = [m for m in height_encoder if getattr(m, "weight", None) is not None and m.weight.dim() == 4]
-        projs = [m for m in gat_project_layer if getattr(m, "weight", None) is not None and m.weight.dim() == 2]
+        convs, projs = self._weighted(height_encoder, 4), self._weighted(gat_project_layer, 2)
         if len(convs) != 3 or len(projs) != 2:
             raise ValueError("order_embed: three Conv2d and two Linear (gat_project_layer)")
         if getattr(embedder, "init_embed", None) is not None:
@@ -1486,7 +1537,7 @@ class OrderEmbedWeights(object):
         att, ff = layers[0][0].module, layers[0][1].module
         if int(getattr(att, "n_heads", 1)) != 1:
             raise ValueError("order_embed: one attention head")
-        ffs = [m for m in ff if getattr(m, "weight", None) is not None and m.weight.dim() == 2] if hasattr(ff, "__iter__") else []
+        ffs = self._weighted(ff, 2) if hasattr(ff, "__iter__") else []
         if len(ffs) != 2:
             raise ValueError("order_embed: the feed-forward pair Linear ReLU Linear")
         qkv = (att.W_query, att.W_key, att.W_val)
@@ -1495,56 +1546,15 @@ class OrderEmbedWeights(object):
         self.layers = tuple(convs + projs) + qkv + (att.W_out,) + tuple(ffs)
         if any(m.bias is None for m in convs + projs + [att.W_out] + ffs):
             raise ValueError("order_embed: every other layer has a bias")
-        self.slope, self.map_len = float(negative_slope), int(map_len)
-        for m, (ks, s, p) in zip(convs, ((4, 2, 1), (4, 2, 1), (3, 1, 1))):
-            if tuple(m.weight.shape[2:]) != (ks, ks) or tuple(getattr(m, "stride", (s, s))) != (s, s) or \
-                    tuple(getattr(m, "padding", (p, p))) != (p, p):
-                raise ValueError("order_embed: Conv2d(1, c1, 4, 2, 1), Conv2d(c1, c2, 4, 2, 1), Conv2d(c2, c3, 3, 1, 1)")
-        self.c1, self.c2, self.c3 = (int(m.weight.shape[0]) for m in convs)
+        self._encoder(convs, negative_slope, map_len)
         self.proj_hidden, self.embed = int(projs[0].weight.shape[0]), int(projs[1].weight.shape[0])
         self.ff_hidden = int(ffs[0].weight.shape[0])
-        if self.map_len % 4 != 0 or not 8 <= self.map_len <= 32:
-            raise ValueError("order_embed: map_len is a multiple of 4 in [8, 32]")
-        self.map_feat = self.c3 * (self.map_len // 4) ** 2
         self.feat = int(projs[0].weight.shape[1]) - self.map_feat
         E = self.embed
-        want = [(self.c1, 1, 4, 4), (self.c2, self.c1, 4, 4), (self.c3, self.c2, 3, 3), (self.proj_hidden, self.feat + self.map_feat),
-                (E, self.proj_hidden), (E, E), (E, E), (E, E), (E, E), (self.ff_hidden, E), (E, self.ff_hidden)]
-        for m, shape in zip(self.layers, want):
-            if tuple(m.weight.shape) != shape or (m.bias is not None and tuple(m.bias.shape) != shape[:1]):
-                raise ValueError(f"order_embed: a weight of shape {tuple(m.weight.shape)} beside the expected {shape}")
-        if not (1 <= self.c1 <= 16 and 1 <= self.c2 <= 32 and 1 <= self.c3 <= 4 and self.slope >= 0 and
-                all(1 <= v <= ORDER_MAX_WIDTH for v in (self.feat, self.proj_hidden, E, self.ff_hidden))):
-            raise ValueError("order_embed: 1 <= c1 <= 16, 1 <= c2 <= 32, 1 <= c3 <= 4, 1 <= feat, proj_hidden, embed, ff_hidden <= 256 "
-                             "and negative_slope >= 0")
+        self._finish([(self.c1, 1, 4, 4), (self.c2, self.c1, 4, 4), (self.c3, self.c2, 3, 3), (self.proj_hidden, self.feat + self.map_feat),
+                      (E, self.proj_hidden), (E, E), (E, E), (E, E), (E, E), (self.ff_hidden, E), (E, self.ff_hidden)])
         import numpy as np
         self.norm = float(np.float32(1.0 / np.sqrt(np.float64(E))))     # nf: 1 / sqrt(E) in float64, rounded to float32 once
-        self.device = convs[0].weight.device
-        self._workspace = {}
-        self.refresh()
-
-    @classmethod
-    def from_layers(cls, height_encoder, gat_project_layer, embedder, negative_slope: float = 0.01, *,
-                    map_len: int = 32) -> "OrderEmbedWeights":
-        return cls(height_encoder, gat_project_layer, embedder, negative_slope, map_len=map_len)
-
-    @torch.no_grad()
-    def refresh(self) -> "OrderEmbedWeights":
-        names = iter(_ORDER_FIELDS)
-        for m in self.layers:
-            setattr(self, next(names), _f32(m.weight.detach(), self.device).clone())
-            if m.bias is not None:
-                setattr(self, next(names), _f32(m.bias.detach(), self.device).clone())
-        return self
-
-    def _struct(self) -> _IrbppOrderEmbedWeights:
-        return _IrbppOrderEmbedWeights(*(getattr(self, n).data_ptr() for n in _ORDER_FIELDS), *(getattr(self, n) for n in _ORDER_SIZES),
-                                       self.slope)
-
-    def _base(self, n_env: int) -> torch.Tensor:
-        if n_env not in self._workspace:
-            self._workspace = {n_env: torch.empty((n_env, self.proj_hidden), dtype=torch.float32, device=self.device)}
-        return self._workspace[n_env]
 
 
 def _dexp_np(t):
@@ -1563,17 +1573,13 @@ def _dexp_np(t):
 
 def _order_embed_cpu(state: torch.Tensor, sf: torch.Tensor, w: OrderEmbedWeights, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     import numpy as np
-    f32 = np.float32
-    n = lambda t: t.detach().to(torch.float32).cpu().numpy()  # noqa: E731
+    f32, n = np.float32, _np32
     leaky = lambda s: np.where(s > 0, s, f32(w.slope) * s).astype(f32)  # noqa: E731
     relu = lambda s: np.where(s > 0, s, f32(0)).astype(f32)  # noqa: E731
     obs, sf = n(state), n(sf)
-    N, L, F_, M, E = obs.shape[0], w.map_len, w.feat, w.map_feat, w.embed
+    N, L, F_, E = obs.shape[0], w.map_len, w.feat, w.embed
     with np.errstate(all="ignore"):
-        hm = obs[:, k:k + L * L].reshape(N, 1, L, L)
-        a = leaky(_conv_np(hm, n(w.w_conv1), n(w.b_conv1), 2, 1))
-        a = leaky(_conv_np(a, n(w.w_conv2), n(w.b_conv2), 2, 1))
-        fmap = leaky(_conv_np(a, n(w.w_conv3), n(w.b_conv3), 1, 1)).reshape(N, M)
+        fmap = _height_map_np(obs[:, k:k + L * L].reshape(N, 1, L, L), w, leaky)
         w_g1 = n(w.w_g1)
         base = _chain_np(np.broadcast_to(n(w.b_g1), (N, w.proj_hidden)).astype(f32), w_g1[:, F_:], fmap)     # the map goes first
         g = leaky(_chain_np(np.broadcast_to(base[:, None, :], (N, k, w.proj_hidden)), w_g1[:, :F_], sf))
@@ -1601,10 +1607,7 @@ def _order_embed_cpu(state: torch.Tensor, sf: torch.Tensor, w: OrderEmbedWeights
 def _order_embed_torch(state: torch.Tensor, sf: torch.Tensor, w: OrderEmbedWeights, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     F = torch.nn.functional
     N, L, F_ = state.shape[0], w.map_len, w.feat
-    hm = state[:, k:k + L * L].reshape(N, 1, L, L)
-    a = F.leaky_relu(F.conv2d(hm, w.w_conv1, w.b_conv1, stride=2, padding=1), w.slope)
-    a = F.leaky_relu(F.conv2d(a, w.w_conv2, w.b_conv2, stride=2, padding=1), w.slope)
-    fmap = F.leaky_relu(F.conv2d(a, w.w_conv3, w.b_conv3, stride=1, padding=1), w.slope).reshape(N, -1)
+    fmap = _height_map_torch(state[:, k:k + L * L].reshape(N, 1, L, L), w)
     base = F.linear(fmap, w.w_g1[:, F_:], w.b_g1)                                # once per bin, not once per slot
     h0 = F.linear(F.leaky_relu(F.linear(sf, w.w_g1[:, :F_]).add_(base[:, None, :]), w.slope), w.w_g2, w.b_g2)
     q, key, v = F.linear(h0, w.w_q), F.linear(h0, w.w_k), F.linear(h0, w.w_v)
@@ -1642,9 +1645,7 @@ def order_embed(state: torch.Tensor, shape_feature: torch.Tensor, weights: Order
     k = _order_slots(state, w)
     N, E, F_ = int(state.shape[0]), w.embed, w.feat
     dev = w.device
-    state = state.detach().to(device=dev, dtype=torch.float32)
-    if state.stride(1) != 1 or (N > 1 and state.stride(0) < state.shape[1]):
-        state = state.contiguous()
+    state = _front_state(state, dev)
     sf = shape_feature.detach().to(device=dev, dtype=torch.float32)
     if tuple(sf.shape) not in ((N * k, F_), (N, k, F_)):
         raise ValueError(f"shape_feature must be [{N * k}, {F_}] or [{N}, {k}, {F_}]")
@@ -1652,34 +1653,16 @@ def order_embed(state: torch.Tensor, shape_feature: torch.Tensor, weights: Order
         sf = sf.reshape(N * k, F_)                       # a view where the strides allow it, else a copy
     if (F_ > 1 and sf.stride(1) != 1) or sf.stride(0) < F_:
         sf = sf.contiguous()
-    if out is not None and (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (N, k, E) or
-                            (E > 1 and out.stride(2) != 1) or out.stride(1) < E or
-                            (N > 1 and out.stride(0) < (k - 1) * int(out.stride(1)) + E)):
-        raise ValueError(f"out must be a float32 [{N}, {k}, {E}] tensor on the weights' device with contiguous rows")
-    if out_global is not None and (out_global.dtype != torch.float32 or out_global.device != dev or
-                                   tuple(out_global.shape) != (N, E) or (E > 1 and out_global.stride(1) != 1) or
-                                   (N > 1 and out_global.stride(0) < E)):
-        raise ValueError(f"out_global must be a float32 [{N}, {E}] tensor on the weights' device with contiguous rows")
     lib = _head_lib(w.w_g1, use_hip, ORDER_EMBED_HIP_DEFAULT)
+    out, out_global, env_stride, row_stride, xg_stride = _front_out(out, out_global, N, k, E, dev, lib is not None)
     if lib is None:
-        x, xg = _order_embed_torch(state, sf.reshape(N, k, F_), w, k) if dev.type == "cuda" else \
-            _order_embed_cpu(state, sf.reshape(N, k, F_), w, k)
-        if out is not None:
-            x = out.copy_(x)
-        if out_global is not None:
-            xg = out_global.copy_(xg)
-        return x, xg
+        sf = sf.reshape(N, k, F_)
+        return _front_copy(*(_order_embed_torch(state, sf, w, k) if dev.type == "cuda" else _order_embed_cpu(state, sf, w, k)), out, out_global)
     from . import _lib
-    if out is None:
-        out = torch.empty((N, k, E), dtype=torch.float32, device=dev)
-    if out_global is None:
-        out_global = torch.empty((N, E), dtype=torch.float32, device=dev)
-    row_stride = int(out.stride(1))
-    env_stride = int(out.stride(0)) if N > 1 else (k - 1) * row_stride + E
     ws = w._struct()
     _lib.check(lib.irbpp_order_embed(C.byref(ws), _p(state), int(state.stride(0)) if N > 1 else int(state.shape[1]), _p(sf),
                                      int(sf.stride(0)), k, N, _p(w._base(N)), _p(out), env_stride, row_stride, _p(out_global),
-                                     int(out_global.stride(0)) if N > 1 else E, _stream(dev)), "irbpp_order_embed")
+                                     xg_stride, _stream(dev)), "irbpp_order_embed")
     return out, out_global
 
 

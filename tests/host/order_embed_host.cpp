@@ -1,6 +1,6 @@
 // Host harness (test infrastructure): the two kernels of irbpp_amd/csrc/irbpp_order_embed.hip run on the CPU, one workgroup at
-// a time, its threads in lockstep (lockstep.h).  The kernels' own source is compiled (with irbpp_embed.hip in front of it, whose
-// embed_conv and embed_chain it uses), so the tiles of whole bins, the idle lanes, the LDS regions that take turns, the blocks
+// a time, its threads in lockstep (lockstep.h).  The kernels' own source is compiled (that file alone: what it shares with
+// irbpp_embed.hip it includes itself, irbpp_front.h), so the tiles of whole bins, the idle lanes, the LDS regions that take turns, the blocks
 // of Q and K, the compatibility chains in registers and the softmax are what the CPU suite checks against the numpy
 // definition; fmaf is the C library's, a single rounding (build with -ffp-contract=off).  host_order_embed repeats the launches
 // of irbpp_order_embed (irbpp_capi.hip) after its argument checks; the rows kernel's dynamic LDS is a heap block of exactly the
@@ -11,7 +11,6 @@
 
 #include "lockstep.h"
 
-#include "../../irbpp_amd/csrc/irbpp_embed.hip"
 #include "../../irbpp_amd/csrc/irbpp_order_embed.hip"
 
 // w: the 19 arrays in irbpp_order_embed_weights' order; sizes: map_len, c1, c2, c3, feat, proj_hidden, embed, ff_hidden.
