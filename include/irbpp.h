@@ -796,6 +796,32 @@ int irbpp_order_embed(const irbpp_order_embed_weights* w, const float* obs_dev, 
                       int32_t k_slots, int32_t n_env, float* base_dev /* workspace [n_env][proj_hidden] */,
                       float* x_dev, int64_t env_stride, int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream);
 
+/* One parameter tensor of the optimiser step: float32, contiguous, numel elements, 4-byte alignment is enough (16-byte
+ * aligned bases take 16-byte accesses).  target may be NULL (nothing is copied for that tensor). */
+typedef struct { float *param, *grad, *exp_avg, *exp_avg_sq, *target; int64_t numel; } irbpp_optim_tensor;
+#define IRBPP_ADAM_WRITE_GRADS 1   /* store the clipped gradient back, as clip_grad_norm_ leaves it                          */
+#define IRBPP_ADAM_ZERO_GRADS  2   /* store 0.0f in its place: the next step's zero_grad, with stable gradient pointers     */
+#define IRBPP_ADAM_SYNC_TARGET 4   /* store the new parameter to `target` as well: update_target_net for the parameters      */
+#define IRBPP_ADAM_CLIP_ONLY   8   /* no Adam: the gradients are scaled and written back, clip_grad_norm_ alone             */
+/* step_size = (float)(lr / (1 - beta1^t)) and rsq = (float)sqrt(1 - beta2^t), computed in float64 for the 1-based step t;
+ * one_minus_beta1/2 the float32 values the update multiplies by. */
+typedef struct { float step_size, rsq, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, max_norm; int32_t flags; } irbpp_adam_hyper;
+/* replaces: clip_grad_norm_(online_net.parameters(), norm_clip) and optimiser.step() of optim.Adam (agent.py:120-121, 44), with
+ * IRBPP_ADAM_ZERO_GRADS the next online_net.zero_grad() and with IRBPP_ADAM_SYNC_TARGET update_target_net's copy of the
+ * parameters (agent.py:127-128), in two launches on `stream` over all tensors at once.  tensors_dev: the n_tensors tensors
+ * that take part; chunks_dev: int32 [n_chunks][2] = (tensor, first element), every tensor cut into chunks of 1024 elements
+ * in ascending order, its last chunk short (numel < 2^31); partial_dev: workspace float64 [n_chunks].  The arithmetic is
+ * defined (csrc/irbpp_optim.hip: the squares summed in float64 in one fixed order without atomics, total = (float)sqrt(sum),
+ * coef = max_norm / (total + 1e-6f) where that is < 1 and else 1, torch's Adam update with two fmaf) and reproducible bit for
+ * bit.  total_norm_dev float32[1] receives total.  A sum whose exponent field is all ones (an infinite or NaN gradient)
+ * skips the step: no tensor is written, *skipped_dev goes up by one, total is +inf or the NaN 0x7fc00000.  `hyper` is host
+ * memory, read at the call.  The tables are device data and are not checked: a wrong entry is an out-of-range access.
+ * IRBPP_ERR_ARG, before anything is launched, if a pointer is NULL, n_tensors < 1, n_chunks < n_tensors, flags has an
+ * unknown bit, WRITE_GRADS together with ZERO_GRADS, or CLIP_ONLY together with ZERO_GRADS or SYNC_TARGET. */
+int irbpp_clipped_adam_step(const irbpp_optim_tensor* tensors_dev, int32_t n_tensors, const int32_t* chunks_dev, int32_t n_chunks,
+                            double* partial_dev, const irbpp_adam_hyper* hyper /* host, read at the call */,
+                            float* total_norm_dev, int64_t* skipped_dev, void* stream);
+
 /* Tooling: when cycles_dev != NULL every later transition launch stores, per bin, one row
  * int64[num_bins][16]: shader-clock stamps 0 start, 1 action applied, 2 overlap test done,
  * 3 contour stage done, 4 observation written; 5..7 contour-stage detail; 8/9 the 100 MHz wall

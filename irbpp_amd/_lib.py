@@ -58,6 +58,20 @@ class IrbppStepOut(C.Structure):
                 ("stable_dev", C.c_void_p), ("err_dev", C.c_void_p)]
 
 
+class IrbppOptimTensor(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("target", C.c_void_p), ("numel", C.c_int64)]
+
+
+class IrbppAdamHyper(C.Structure):
+    _fields_ = [("step_size", C.c_float), ("rsq", C.c_float), ("beta1", C.c_float), ("one_minus_beta1", C.c_float),
+                ("beta2", C.c_float), ("one_minus_beta2", C.c_float), ("eps", C.c_float), ("max_norm", C.c_float),
+                ("flags", C.c_int32)]
+
+
+ADAM_WRITE_GRADS, ADAM_ZERO_GRADS, ADAM_SYNC_TARGET, ADAM_CLIP_ONLY = 1, 2, 4, 8
+
+
 # every entry point include/irbpp.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "irbpp_status_string": (C.c_char_p, [C.c_int]),
@@ -143,6 +157,8 @@ SIGNATURES = {
                                      C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "irbpp_dueling_loss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
+    "irbpp_clipped_adam_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(IrbppAdamHyper), C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
     "irbpp_noisy_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "irbpp_streams_act": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,

@@ -26,6 +26,7 @@
 #include "irbpp_c51.hip"            // the distributional head around the network (irbpp_categorical_act, irbpp_categorical_target)
 #include "irbpp_dueling.hip"        // the same from the network's logits: dueling combine + softmax fused in (irbpp_dueling_act, irbpp_dueling_target)
 #include "irbpp_dueling_loss.hip"   // the loss that carries the gradient, forward and backward from the logits (irbpp_dueling_loss, irbpp_dueling_loss_backward)
+#include "irbpp_optim.hip"          // the optimiser step: gradient-norm clip and Adam over all parameter tensors, two launches (irbpp_clipped_adam_step)
 #include "irbpp_streams.hip"        // the four noisy layers of the value and advantage streams in front of the dueling head (irbpp_noisy_weights, irbpp_streams_act)
 #include "irbpp_shapefeat.hip"      // the shape branch in front of the network: sampled points to shape features (irbpp_shape_features)
 #include "irbpp_embed.hip"          // the embedding stage: heightmap CNN, candidate rows, masked mean (irbpp_embed)
@@ -1215,6 +1216,24 @@ int irbpp_dueling_loss_backward(const float* g_dev, const float* grad_loss_dev, 
     const int chunks = grad_a_out_dev ? (s_rows + DUELING_LOSS_CHUNK_ROWS - 1) / DUELING_LOSS_CHUNK_ROWS : 1;
     hipLaunchKernelGGL(irbpp_dueling_loss_backward_kernel, dim3(batch, chunks), dim3(DUELING_THREADS), 0, (hipStream_t)stream,
                        g_dev, grad_loss_dev, actions_dev, atoms, s_rows, grad_v_out_dev, grad_a_out_dev);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+int irbpp_clipped_adam_step(const irbpp_optim_tensor* tensors_dev, int32_t n_tensors, const int32_t* chunks_dev, int32_t n_chunks,
+                            double* partial_dev, const irbpp_adam_hyper* hyper, float* total_norm_dev, int64_t* skipped_dev,
+                            void* stream) {
+    if (!tensors_dev || !chunks_dev || !partial_dev || !hyper || !total_norm_dev || !skipped_dev || n_tensors < 1 ||
+        n_chunks < n_tensors)
+        return IRBPP_ERR_ARG;
+    const int32_t f = hyper->flags;
+    if ((f & ~(IRBPP_ADAM_WRITE_GRADS | IRBPP_ADAM_ZERO_GRADS | IRBPP_ADAM_SYNC_TARGET | IRBPP_ADAM_CLIP_ONLY)) ||
+        ((f & IRBPP_ADAM_WRITE_GRADS) && (f & IRBPP_ADAM_ZERO_GRADS)) ||
+        ((f & IRBPP_ADAM_CLIP_ONLY) && (f & (IRBPP_ADAM_ZERO_GRADS | IRBPP_ADAM_SYNC_TARGET))))
+        return IRBPP_ERR_ARG;
+    hipLaunchKernelGGL(irbpp_grad_sumsq_kernel, dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, tensors_dev, chunks_dev,
+                       partial_dev);
+    hipLaunchKernelGGL(irbpp_clipped_adam_kernel, dim3(n_chunks), dim3(OPTIM_THREADS), 0, (hipStream_t)stream, tensors_dev, chunks_dev,
+                       (const double*)partial_dev, (int)n_chunks, *hyper, total_norm_dev, (long long*)skipped_dev);
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
 }
 

@@ -839,6 +839,14 @@ def learn_loss(online_logits, target_logits, batch, support: torch.Tensor, gamma
         optimiser.step()
         memory.update_priorities(tree_idxs, loss.detach())
 
+    or, with ``optimiser = optim.ClippedAdam(online_net.parameters(), lr, betas, eps, norm_clip, grads="zero",
+    target_params=target_net.parameters())`` (irbpp_amd/optim.py: the clip, Adam, the next zero_grad and the target's
+    parameter copy as two launches)::
+
+        (weights * loss).mean().backward()
+        optimiser.step(sync_target=T % target_update == 0)
+        memory.update_priorities(tree_idxs, loss.detach())
+
     ``use_hip`` is handed to both head calls (``None``: each one's own default)."""
     _, states, actions, returns, next_states, nonterminals, _ = batch
     v, a = online_logits(states)
