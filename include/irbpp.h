@@ -687,6 +687,17 @@ int irbpp_streams_act(const irbpp_stream_weights* w, const float* xg_dev, int64_
                       int32_t s_rows, int32_t n_env, int64_t* action_dev /* may be NULL when only logits are wanted */,
                       float* q_out_dev, int64_t q_stride, float* v_out_dev, float* a_out_dev, void* stream);
 
+/* irbpp_streams_act with the advantage stream on the matrix cores (csrc/irbpp_streams_mfma.hip, csrc/irbpp_mfma_chain.h): the
+ * same arguments, the same outputs and the same definition, and the bits are those of irbpp_streams_act -- the float32
+ * matrix instruction of gfx950 rounds once per product and accumulates in k order, so with the accumulator started from the
+ * bias and the k-steps issued ascending every output is the chain of the definition.  Same workspace rule above the 144 KB
+ * tile (the second launch is irbpp_streams_act's own), same limits, and embed % 4 == 0 and hidden % 4 == 0 (k is never
+ * padded): IRBPP_ERR_ARG otherwise, never another form in its place. */
+int irbpp_streams_act_mfma(const irbpp_stream_weights* w, const float* xg_dev, int64_t xg_stride, const float* x_dev,
+                           int64_t env_stride, int64_t row_stride, const float* support_dev, const float* obs_dev,
+                           int32_t obs_stride, int32_t s_rows, int32_t n_env, int64_t* action_dev /* may be NULL */,
+                           float* q_out_dev, int64_t q_stride, float* v_out_dev, float* a_out_dev, void* stream);
+
 /* The shape encoder (model.py: shapeEncoder = Linear(3, hidden) LeakyReLU Linear(hidden, feat) LeakyReLU), float32 on the
  * device, row-major and contiguous: w1 [hidden][3], b1 [hidden], w2 [feat][hidden], b2 [feat]; slope is the LeakyReLU's
  * negative_slope (0.01 in the reference), >= 0. */

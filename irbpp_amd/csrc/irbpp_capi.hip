@@ -28,6 +28,7 @@
 #include "irbpp_dueling_loss.hip"   // the loss that carries the gradient, forward and backward from the logits (irbpp_dueling_loss, irbpp_dueling_loss_backward)
 #include "irbpp_optim.hip"          // the optimiser step: gradient-norm clip and Adam over all parameter tensors, two launches (irbpp_clipped_adam_step)
 #include "irbpp_streams.hip"        // the four noisy layers of the value and advantage streams in front of the dueling head (irbpp_noisy_weights, irbpp_streams_act)
+#include "irbpp_streams_mfma.hip"   // the same launch with the advantage stream on the matrix cores, the same bits (irbpp_streams_act_mfma)
 #include "irbpp_shapefeat.hip"      // the shape branch in front of the network: sampled points to shape features (irbpp_shape_features)
 #include "irbpp_embed.hip"          // the embedding stage: heightmap CNN, candidate rows, masked mean (irbpp_embed)
 #include "irbpp_order_embed.hip"    // the order network's embedding stage: CNN, k buffered items, one attention layer, mean (irbpp_order_embed)
@@ -1265,6 +1266,38 @@ int irbpp_streams_act(const irbpp_stream_weights* w, const float* xg_dev, int64_
     g.embed = w->embed, g.hidden = w->hidden, g.atoms = w->atoms, g.obs_stride = obs_stride, g.s_rows = s_rows;
     g.x_vec4 = ((uintptr_t)x_dev % 16 == 0 && (uintptr_t)w->w_ha % 16 == 0 && env_stride % 4 == 0 && row_stride % 4 == 0 && w->embed % 4 == 0) ? 1 : 0;
     const auto kernel = w->atoms <= 32 ? irbpp_streams_act_a32_kernel : irbpp_streams_act_kernel;
+    size_t lds = 0;
+    if (resident && !dueling_lds((const void*)kernel, w->atoms, s_rows, &lds)) return IRBPP_ERR_HIP;
+    hipLaunchKernelGGL(kernel, dim3(n_env), dim3(DUELING_THREADS), lds, (hipStream_t)stream, w->w_hv, w->b_hv, w->w_zv, w->b_zv,
+                       w->w_ha, w->b_ha, w->w_za, w->b_za, xg_dev, x_dev, support_dev, obs_dev, action_dev, q_out_dev, v_out_dev,
+                       a_out_dev, g);
+    if (hipGetLastError() != hipSuccess) return IRBPP_ERR_HIP;
+    if (resident || (!action_dev && !q_out_dev)) return IRBPP_OK;
+    if (!dueling_lds((const void*)irbpp_streams_finish_kernel, w->atoms, s_rows, &lds)) return IRBPP_ERR_HIP;
+    hipLaunchKernelGGL(irbpp_streams_finish_kernel, dim3(n_env), dim3(DUELING_THREADS), lds, (hipStream_t)stream, w->w_hv, w->b_hv,
+                       w->w_zv, w->b_zv, xg_dev, (const float*)a_out_dev, support_dev, obs_dev, action_dev, q_out_dev, g);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+int irbpp_streams_act_mfma(const irbpp_stream_weights* w, const float* xg_dev, int64_t xg_stride, const float* x_dev,
+                           int64_t env_stride, int64_t row_stride, const float* support_dev, const float* obs_dev, int32_t obs_stride,
+                           int32_t s_rows, int32_t n_env, int64_t* action_dev, float* q_out_dev, int64_t q_stride, float* v_out_dev,
+                           float* a_out_dev, void* stream) {
+    if (!w || !w->w_hv || !w->b_hv || !w->w_zv || !w->b_zv || !w->w_ha || !w->b_ha || !w->w_za || !w->b_za || w->embed < 1 ||
+        w->embed > STREAMS_MAX_WIDTH || w->hidden < 1 || w->hidden > STREAMS_MAX_WIDTH || w->embed % 4 || w->hidden % 4 ||
+        w->atoms < 2 || w->atoms > HEAD_MAX_ATOMS || s_rows < 1 || s_rows > HEAD_MAX_ROWS || n_env < 1 || !xg_dev ||
+        xg_stride < w->embed || !x_dev || row_stride < w->embed || env_stride < (int64_t)(s_rows - 1) * row_stride + w->embed ||
+        (obs_dev && obs_stride < 5 * s_rows) || (q_out_dev && q_stride < s_rows) || ((action_dev || q_out_dev) && !support_dev) ||
+        (!action_dev && !q_out_dev && !v_out_dev && !a_out_dev))
+        return IRBPP_ERR_ARG;
+    const bool resident = dueling_tile_rows(s_rows, w->atoms) == s_rows;
+    if (!resident && !a_out_dev) return IRBPP_ERR_ARG;                         // the block needs a_out as its workspace
+    StreamsArgs g;
+    g.xg_stride = xg_stride, g.env_stride = env_stride, g.row_stride = row_stride, g.q_stride = q_stride;
+    g.embed = w->embed, g.hidden = w->hidden, g.atoms = w->atoms, g.obs_stride = obs_stride, g.s_rows = s_rows;
+    g.x_vec4 = (((uintptr_t)x_dev % 16 == 0 && env_stride % 4 == 0 && row_stride % 4 == 0) ? STREAMS_MFMA_X16 : 0) |
+               ((uintptr_t)w->w_ha % 16 == 0 ? STREAMS_MFMA_WHA16 : 0) | ((uintptr_t)w->w_za % 16 == 0 ? STREAMS_MFMA_WZA16 : 0);
+    const auto kernel = w->atoms <= MFMA_TILE ? irbpp_streams_act_mfma_a32_kernel : irbpp_streams_act_mfma_kernel;
     size_t lds = 0;
     if (resident && !dueling_lds((const void*)kernel, w->atoms, s_rows, &lds)) return IRBPP_ERR_HIP;
     hipLaunchKernelGGL(kernel, dim3(n_env), dim3(DUELING_THREADS), lds, (hipStream_t)stream, w->w_hv, w->b_hv, w->w_zv, w->b_zv,

@@ -134,6 +134,41 @@ struct StreamsArgs {
     int embed, hidden, atoms, obs_stride, s_rows, x_vec4;
 };
 
+// The a block of one environment stands in the tile (pitch atoms | 1; a barrier has passed since it was written), sh.v and
+// sh.z are set: the logits to a_out, then the resident form of dueling_block_argmax on the tile as it stands.  Shared with
+// irbpp_streams_mfma.hip.
+__device__ __forceinline__ void streams_tile_finish(float* tile, DuelingShared& sh, const float* __restrict__ flags, const StreamsArgs& g,
+                                                    int64_t* __restrict__ action, float* __restrict__ q_out, float* __restrict__ a_out) {
+    const int tid = threadIdx.x, atoms = g.atoms, s_rows = g.s_rows, pitch = atoms | 1;
+    if (a_out) head_walk<DUELING_THREADS>(atoms, s_rows, [&](int row, int k, int e) { a_out[e] = tile[row * pitch + k]; });
+    if (!action && !q_out) return;                       // only the logits were wanted
+    dueling_mean(tile, pitch, atoms, s_rows, sh.part, sh.mean);
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = tid; i < s_rows; i += DUELING_THREADS) {
+        const float s = dueling_row(tile + i * pitch, sh.v, sh.mean, sh.z, atoms);
+        if (q_out) q_out[i] = s;
+        const float val = head_masked(flags, i, s);
+        if (head_better(val, i, best, bi)) { best = val; bi = i; }
+    }
+    head_wave_argmax(best, bi);
+    if ((tid & 63) == 0) {
+        sh.best[tid >> 6] = best;
+        sh.bi[tid >> 6] = bi;
+    }
+    __syncthreads();
+    if (tid == 0 && action) {
+        best = sh.best[0];
+        bi = sh.bi[0];
+        for (int w = 1; w < DUELING_THREADS / 64; ++w) {
+            const float ob = sh.best[w];
+            const int oi = sh.bi[w];
+            if (head_better(ob, oi, best, bi)) { best = ob; bi = oi; }
+        }
+        *action = head_index(bi, s_rows);
+    }
+}
+
 // One workgroup: everything for one environment.  hv: LDS, STREAMS_MAX_WIDTH floats.
 template <int AMAX>
 __device__ __forceinline__ void streams_act_block(const float* __restrict__ w_hv, const float* __restrict__ b_hv,
@@ -170,34 +205,7 @@ __device__ __forceinline__ void streams_act_block(const float* __restrict__ w_hv
     }
     if (!resident) return;
     __syncthreads();
-    if (a_out) head_walk<DUELING_THREADS>(atoms, s_rows, [&](int row, int k, int e) { a_out[e] = tile[row * pitch + k]; });
-    if (!action && !q_out) return;                       // only the logits were wanted
-    dueling_mean(tile, pitch, atoms, s_rows, sh.part, sh.mean);
-    // from here on the resident form of dueling_block_argmax, on the tile as it stands
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = tid; i < s_rows; i += DUELING_THREADS) {
-        const float s = dueling_row(tile + i * pitch, sh.v, sh.mean, sh.z, atoms);
-        if (q_out) q_out[i] = s;
-        const float val = head_masked(flags, i, s);
-        if (head_better(val, i, best, bi)) { best = val; bi = i; }
-    }
-    head_wave_argmax(best, bi);
-    if ((tid & 63) == 0) {
-        sh.best[tid >> 6] = best;
-        sh.bi[tid >> 6] = bi;
-    }
-    __syncthreads();
-    if (tid == 0 && action) {
-        best = sh.best[0];
-        bi = sh.bi[0];
-        for (int w = 1; w < DUELING_THREADS / 64; ++w) {
-            const float ob = sh.best[w];
-            const int oi = sh.bi[w];
-            if (head_better(ob, oi, best, bi)) { best = ob; bi = oi; }
-        }
-        *action = head_index(bi, s_rows);
-    }
+    streams_tile_finish(tile, sh, flags, g, action, q_out, a_out);
 }
 
 #define IRBPP_STREAMS_KERNEL(NAME, AMAX)                                                                                           \

@@ -860,7 +860,9 @@ def learn_loss(online_logits, target_logits, batch, support: torch.Tensor, gamma
 # The same question for the streams in front of the dueling head ("The noisy streams"): torch's layers
 # followed by dueling_greedy_action, since tools/streams_rates.py measured them on an MI355X at 1.79 ms against 5.76 ms for the
 # fused call at 4096 envs and 0.47 ms against 1.46 ms at 1024 (profiles/noisy_streams/): the matrix units win over the defined
-# fmaf chain.  use_hip=True asks for the kernels (the reproducible forward).
+# fmaf chain.  use_hip=True asks for the kernels (the reproducible forward).  form="mfma" runs the same chains on the matrix
+# cores, the same bits: 2.38 ms and 0.62 ms at the two sizes in a later run of the same tool ("The noisy
+# streams on the matrix cores"), still behind torch's layers, so the default stays.
 STREAMS_HIP_DEFAULT = False
 
 STREAMS_MAX_WIDTH, STREAMS_MAX_ATOMS, STREAMS_MAX_ROWS = 256, 128, 1024
@@ -972,8 +974,22 @@ def _streams_inputs(x: torch.Tensor, x_global: torch.Tensor, w: StreamWeights) -
     return _c51_block(x), _dueling_v(x_global)
 
 
-def _streams_call(lib, x, xg, w, support, state, q_out, want_action, want_logits):
+STREAMS_FORMS = ("chain", "mfma")
+
+
+def _streams_form(form: str, w: "StreamWeights") -> str:
+    """``form`` of the HIP path: "chain" (irbpp_streams_act, one fmaf chain per thread) or "mfma" (irbpp_streams_act_mfma, the
+    same chains on the matrix cores: the same bits).  "mfma" needs embed and hidden to be multiples of 4 and says so."""
+    if form not in STREAMS_FORMS:
+        raise ValueError(f"streams: form must be one of {STREAMS_FORMS}, not {form!r}")
+    if form == "mfma" and (w.embed % 4 or w.hidden % 4):
+        raise ValueError(f"streams: form='mfma' needs embed and hidden to be multiples of 4 (embed {w.embed}, hidden {w.hidden})")
+    return form
+
+
+def _streams_call(lib, x, xg, w, support, state, q_out, want_action, want_logits, form="chain"):
     from . import _lib
+    name = "irbpp_streams_act_mfma" if form == "mfma" else "irbpp_streams_act"
     N, S, _ = x.shape
     dev = x.device
     fits = S * (w.atoms | 1) * 4 <= 144 * 1024           # DUELING_TILE_BYTES: a larger block needs a_out as its workspace
@@ -983,16 +999,15 @@ def _streams_call(lib, x, xg, w, support, state, q_out, want_action, want_logits
     v = torch.empty((N, w.atoms), dtype=torch.float32, device=dev) if want_logits else None
     a = torch.empty((N, S, w.atoms), dtype=torch.float32, device=dev) if want_logits or not fits else None
     ws = w._struct()
-    _lib.check(lib.irbpp_streams_act(C.byref(ws), _p(xg), xg.stride(0), _p(x), x.stride(0), x.stride(1), _p(support), _p(state),
-                                     obs_stride, S, N, _p(action), _p(q_out), q_stride, _p(v), _p(a), _stream(dev)),
-               "irbpp_streams_act")
+    _lib.check(getattr(lib, name)(C.byref(ws), _p(xg), xg.stride(0), _p(x), x.stride(0), x.stride(1), _p(support), _p(state),
+                                  obs_stride, S, N, _p(action), _p(q_out), q_stride, _p(v), _p(a), _stream(dev)), name)
     return action, v, a
 
 
 @torch.no_grad()
 def streams_greedy_action(x: torch.Tensor, x_global: torch.Tensor, weights: StreamWeights, support: torch.Tensor,
                           state: Optional[torch.Tensor] = None, *, q_out: Optional[torch.Tensor] = None,
-                          use_hip: Optional[bool] = None) -> torch.Tensor:
+                          use_hip: Optional[bool] = None, form: str = "chain") -> torch.Tensor:
     """The last stage of DQNBPP.forward (model.py:393-400: the four noisy layers of the value and advantage streams, the
     combine and the softmax) and all of Agent.act after it (agent.py:51-58), from the embeddings ``x`` [N, S, E] and
     ``x_global`` [N, E] (or [N, 1, E]) -> int64[N].  ``weights``: a StreamWeights; ``support`` / ``state`` / ``q_out`` as in
@@ -1000,26 +1015,28 @@ def streams_greedy_action(x: torch.Tensor, x_global: torch.Tensor, weights: Stre
     in a defined float32 arithmetic (irbpp_streams_act: every layer output one ascending fmaf chain, then the arithmetic of
     irbpp_dueling_act; neither the hidden block nor the logits reach memory).  Otherwise the same definition runs in two steps:
     streams_logits (on the CPU an exact numpy emulation of the chains, on a HIP device torch's layers) and
-    dueling_greedy_action."""
+    dueling_greedy_action.  ``form`` chooses between the two kernels of the HIP path, which give the same bits: "chain"
+    (irbpp_streams_act) or "mfma" (irbpp_streams_act_mfma, the chains on the matrix cores; embed and hidden multiples of 4, a
+    ValueError otherwise); the other paths have one form and ignore it."""
     x, xg = _streams_inputs(x, x_global, weights)
     lib = _head_lib(x, use_hip, STREAMS_HIP_DEFAULT)
     if lib is None:
         v, a = streams_logits(x, xg, weights, use_hip=False)
         return dueling_greedy_action(v, a, support, state, None, q_out, use_hip=None if x.is_cuda else False)
-    return _streams_call(lib, x, xg, weights, _f32(support, x.device), state, q_out, True, False)[0]
+    return _streams_call(lib, x, xg, weights, _f32(support, x.device), state, q_out, True, False, _streams_form(form, weights))[0]
 
 
 @torch.no_grad()
 def streams_logits(x: torch.Tensor, x_global: torch.Tensor, weights: StreamWeights, *,
-                   use_hip: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                   use_hip: Optional[bool] = None, form: str = "chain") -> Tuple[torch.Tensor, torch.Tensor]:
     """The value and advantage streams alone, without a gradient: -> (v float32 [N, atoms], a float32 [N, S, atoms]), what
     dueling_c51_target consumes (the two no_grad network calls of Agent.learn, agent.py:90, 96).  Forms as in
     streams_greedy_action; on a HIP device without the kernels torch's ``F.linear`` / ``relu`` lines run (rocBLAS's own
-    summation order: close to, not bit-equal with, the definition)."""
+    summation order: close to, not bit-equal with, the definition).  ``form`` as in streams_greedy_action."""
     x, xg = _streams_inputs(x, x_global, weights)
     lib = _head_lib(x, use_hip, STREAMS_HIP_DEFAULT)
     if lib is not None:
-        _, v, a = _streams_call(lib, x, xg, weights, None, None, None, False, True)
+        _, v, a = _streams_call(lib, x, xg, weights, None, None, None, False, True, _streams_form(form, weights))
         return v, a
     if x.is_cuda:
         F = torch.nn.functional
@@ -1489,16 +1506,18 @@ def embed(state: torch.Tensor, shape_feature: torch.Tensor, weights: EmbedWeight
 @torch.no_grad()
 def network_greedy_action(state: torch.Tensor, points: ShapePoints, indices: torch.Tensor, shape_weights: ShapeEncoderWeights,
                           embed_weights: EmbedWeights, stream_weights: StreamWeights, support: torch.Tensor, *,
-                          q_out: Optional[torch.Tensor] = None, use_hip: Optional[bool] = None) -> torch.Tensor:
+                          q_out: Optional[torch.Tensor] = None, use_hip: Optional[bool] = None,
+                          streams_form: str = "chain") -> torch.Tensor:
     """Agent.act from the observation (agent.py:51-58 with all of DQNBPP.forward, bufferSize == 1): ``state`` [N, obs_len] ->
     int64[N], the three stages chained with no torch layer in between: shape_features on the id column ``state[:, 5 S]``,
     embed, streams_greedy_action (which masks by the observation's validity flags).  ``indices``: the forward's one index set
     (``points.draw_indices``); ``q_out`` as in streams_greedy_action; ``use_hip`` is handed to all three (``None``: each
-    one's own default; ``True``: the whole forward in the defined float32 arithmetic, bit for bit what the CPU form gives)."""
+    one's own default; ``True``: the whole forward in the defined float32 arithmetic, bit for bit what the CPU form gives);
+    ``streams_form`` is streams_greedy_action's ``form``."""
     S = _embed_rows(state, embed_weights)
     sf = shape_features(state[:, 5 * S], points, indices, shape_weights, use_hip=use_hip)
     x, xg = embed(state, sf, embed_weights, use_hip=use_hip)
-    return streams_greedy_action(x, xg, stream_weights, support, state.to(x.device), q_out=q_out, use_hip=use_hip)
+    return streams_greedy_action(x, xg, stream_weights, support, state.to(x.device), q_out=q_out, use_hip=use_hip, form=streams_form)
 
 
 # The same question for the order network's embedding stage (DESIGN.md section 3, "The order network"): torch's layers in the
@@ -1677,18 +1696,20 @@ def order_embed(state: torch.Tensor, shape_feature: torch.Tensor, weights: Order
 @torch.no_grad()
 def order_network_greedy_action(state: torch.Tensor, points: ShapePoints, indices: torch.Tensor, shape_weights: ShapeEncoderWeights,
                                 order_weights: OrderEmbedWeights, stream_weights: StreamWeights, support: torch.Tensor, *,
-                                q_out: Optional[torch.Tensor] = None, use_hip: Optional[bool] = None) -> torch.Tensor:
+                                q_out: Optional[torch.Tensor] = None, use_hip: Optional[bool] = None,
+                                streams_form: str = "chain") -> torch.Tensor:
     """The order network's Agent.act from the observation (``orderDQN.act(orderState, None)``, trainer.py:266, with all of
     DQNBPP.forward for bufferSize > 1): ``state`` [N, k + L^2] -> int64[N] in [0, k), the three stages chained with no torch
     layer in between: shape_features on the N k ids ``state[:, :k]`` (one small strided copy makes them contiguous), order_embed,
     streams_greedy_action without a mask.  ``indices``, ``q_out`` and ``use_hip`` as in network_greedy_action (``True``: the
     whole forward in the defined float32 arithmetic, bit for bit what the CPU form gives: on CPU tensors the head is a numpy
-    emulation of irbpp_dueling_act, not streams_greedy_action's torch lines)."""
+    emulation of irbpp_dueling_act, not streams_greedy_action's torch lines); ``streams_form`` is streams_greedy_action's
+    ``form``."""
     k = _order_slots(state, order_weights)
     sf = shape_features(state[:, :k].contiguous(), points, indices, shape_weights, use_hip=use_hip)
     x, xg = order_embed(state, sf, order_weights, use_hip=use_hip)
     if x.is_cuda:
-        return streams_greedy_action(x, xg, stream_weights, support, None, q_out=q_out, use_hip=use_hip)
+        return streams_greedy_action(x, xg, stream_weights, support, None, q_out=q_out, use_hip=use_hip, form=streams_form)
     # the CPU form stays in the defined arithmetic to the end (streams_greedy_action's CPU form ends in torch's softmax)
     v, a = streams_logits(x, xg, stream_weights, use_hip=False)
     _q_out_arg(q_out, int(x.shape[0]), k, x.device, "state")

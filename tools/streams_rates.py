@@ -1,10 +1,11 @@
 #!/usr/bin/env python
-"""Tooling: the last stage of the network in front of the greedy action, two forms in one process, interleaved (the manner of
+"""Tooling: the last stage of the network in front of the greedy action, three forms in one process, interleaved (the manner of
 dueling_head_rates.py):
 
     torch    the parent's path: the four effective weight matrices materialised (mu + sigma * eps), four F.linear and two
              relu (model.py:393-394), then the dueling head kernel (replay.dueling_greedy_action with use_hip=True)
     fused    StreamWeights.refresh() + replay.streams_greedy_action with use_hip=True: irbpp_noisy_weights and one launch
+    mfma     the same with form="mfma": the chains on the matrix cores (irbpp_streams_act_mfma), the same bits
 
     act      x [N, 500, 128], x_global [N, 128], 31 atoms, with the observation's mask, N in --envs (4096 1024)
     logits   the no-grad forward of a learn batch: torch's layers against replay.streams_logits, B in --batches (64)
@@ -64,13 +65,13 @@ def main():
     out = {"S": S, "embed": E, "hidden": H, "atoms": ATOMS, "iters": a.iters, "repeats": a.repeats,
            "device": torch.cuda.get_device_name(0), "act": {}, "logits": {}}
 
-    def fused_act(x, xg, state):
+    def fused_act(x, xg, state, form="chain"):
         w.refresh()
-        return replay.streams_greedy_action(x, xg, w, support, state, use_hip=True)
+        return replay.streams_greedy_action(x, xg, w, support, state, use_hip=True, form=form)
 
-    def fused_logits(x, xg):
+    def fused_logits(x, xg, form="chain"):
         w.refresh()
-        return replay.streams_logits(x, xg, w, use_hip=True)
+        return replay.streams_logits(x, xg, w, use_hip=True, form=form)
 
     with torch.no_grad():
         for kind, sizes in (("act", a.envs), ("logits", a.batches)):
@@ -80,17 +81,21 @@ def main():
                 state[:, :S * 5].view(n, S, 5)[:, :, 4] = (torch.rand((n, S), device=dev, generator=gen) < 0.7).float()
                 if kind == "act":
                     forms = {"torch": lambda: replay.dueling_greedy_action(*logits_torch(layers, x, xg), support, state, S, use_hip=True),
-                             "fused": lambda: fused_act(x, xg, state)}
+                             "fused": lambda: fused_act(x, xg, state), "mfma": lambda: fused_act(x, xg, state, "mfma")}
                     same = (forms["torch"]() == forms["fused"]()).float().mean().item()
+                    fused_same = bool(torch.equal(forms["fused"](), forms["mfma"]()))
                 else:
-                    forms = {"torch": lambda: logits_torch(layers, x, xg), "fused": lambda: fused_logits(x, xg)}
+                    forms = {"torch": lambda: logits_torch(layers, x, xg), "fused": lambda: fused_logits(x, xg),
+                             "mfma": lambda: fused_logits(x, xg, "mfma")}
                     same = None
+                    fused_same = all(torch.equal(c, m) for c, m in zip(forms["fused"](), forms["mfma"]()))
                 r = compare(forms, a.iters, a.repeats)
                 r["x_bytes"] = n * S * E * 4
                 for f in forms:
                     r[f]["x_bytes_per_s"] = r["x_bytes"] / (r[f]["median_ms"] * 1e-3)
                 if same is not None:
                     r["actions_equal_fraction"] = same      # torch's GEMM sums in another order: near-ties may differ
+                r["fused_and_mfma_identical"] = fused_same  # act: every environment's action; logits: every bit of v and a
                 out[kind][str(n)] = r
                 del x, xg, state
     text = json.dumps(out, indent=1)
