@@ -765,6 +765,19 @@ int irbpp_embed(const irbpp_embed_weights* w, const float* obs_dev, int64_t obs_
                 int64_t feat_stride, int32_t s_rows, int32_t n_env, float* base_dev /* workspace [n_env][proj_hidden] */,
                 float* x_dev, int64_t env_stride, int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream);
 
+/* irbpp_embed with the three per-row layers (init_candidate_embed[1], the candidate columns of project_layer[0],
+ * project_layer[1]) on the matrix cores (csrc/irbpp_embed_mfma.hip, csrc/irbpp_mfma_chain.h): the same arguments, workspace,
+ * outputs and definition, two launches on `stream` (irbpp_embed's own bin kernel, then the row kernel of this form).  The
+ * float32 matrix instruction of gfx950 rounds once per product and accumulates in k order, so with the accumulator started
+ * from the chain's start (the bias, base) and the k-steps issued ascending every output is the chain of the definition: x and
+ * xg equal irbpp_embed's bit for bit wherever irbpp_embed's are not NaN, and are NaN where they are (a NaN's payload is not
+ * part of the definition).  Same limits and status codes, and cand_hidden % 4 == 0, cand_embed % 4 == 0 and
+ * proj_hidden % 4 == 0 (the k of the three products is never padded): IRBPP_ERR_ARG otherwise, never another form in its
+ * place. */
+int irbpp_embed_mfma(const irbpp_embed_weights* w, const float* obs_dev, int64_t obs_stride, const float* shape_feat_dev,
+                     int64_t feat_stride, int32_t s_rows, int32_t n_env, float* base_dev /* workspace [n_env][proj_hidden] */,
+                     float* x_dev, int64_t env_stride, int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream);
+
 /* The layers of the order network's embedding stage (model.py, bufferSize > 1: heightEncoder as above; gat_project_layer =
  * Linear(feat + c3 (map_len/4)^2, proj_hidden) LeakyReLU Linear(proj_hidden, embed); embedder = GraphAttentionEncoder with
  * one head and one layer: W_query, W_key, W_val Linear(embed, embed) without a bias, W_out Linear(embed, embed), the

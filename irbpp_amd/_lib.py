@@ -172,6 +172,8 @@ SIGNATURES = {
     "irbpp_shape_features_chunks": (C.c_int, [C.c_int32, C.c_int32]),
     "irbpp_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                               C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "irbpp_embed_mfma": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "irbpp_order_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "irbpp_debug_phase_cycles": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -31,7 +31,8 @@
 #include "irbpp_streams_mfma.hip"   // the same launch with the advantage stream on the matrix cores, the same bits (irbpp_streams_act_mfma)
 #include "irbpp_shapefeat.hip"      // the shape branch in front of the network: sampled points to shape features (irbpp_shape_features)
 #include "irbpp_embed.hip"          // the embedding stage: heightmap CNN, candidate rows, masked mean (irbpp_embed)
-#include "irbpp_order_embed.hip"    // the order network's embedding stage: CNN, k buffered items, one attention layer, mean (irbpp_order_embed)
+#include "irbpp_embed_mfma.hip"     // the same stage with the three per-row layers on the matrix cores, the same bits (irbpp_embed_mfma)
+#include "irbpp_order_embed.hip"   // the order network's embedding stage: CNN, k buffered items, one attention layer, mean (irbpp_order_embed)
 #include "irbpp_metrics.hip"        // the trainer's episode metrics (irbpp_set_episode_window)
 #include "irbpp_itemgen.h"
 #include "irbpp_plan.h"             // which kernels a transition launches: the registry of kernels and plan_transition
@@ -1358,16 +1359,21 @@ static bool front_rows_lds(const void* kernel, size_t bytes) {
     return bytes <= 64 * 1024 || hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
 }
 
-int irbpp_embed(const irbpp_embed_weights* w, const float* obs_dev, int64_t obs_stride, const float* shape_feat_dev,
-                int64_t feat_stride, int32_t s_rows, int32_t n_env, float* base_dev, float* x_dev, int64_t env_stride,
-                int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream) {
+// the two forms of the embedding stage: the bin kernel, then `rows_kernel` (irbpp_embed_rows_kernel or its MFMA form, which
+// needs the K of its three products, width_step = 4, never padded)
+extern "C++" {
+template <typename K>
+static int embed_launch(K rows_kernel, int width_step, const irbpp_embed_weights* w, const float* obs_dev, int64_t obs_stride,
+                        const float* shape_feat_dev, int64_t feat_stride, int32_t s_rows, int32_t n_env, float* base_dev,
+                        float* x_dev, int64_t env_stride, int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream) {
     if (!w || front_encoder_bad(w) || !w->w_c1 || !w->b_c1 || !w->w_c2 || !w->b_c2 || !w->w_p1 || !w->b_p1 || !w->w_p2 ||
         !w->b_p2 || !obs_dev || !shape_feat_dev || !base_dev || !x_dev || !xg_dev || w->feat < 1 || w->feat > EMBED_MAX_WIDTH ||
         w->cand_embed < 1 || w->cand_embed > EMBED_MAX_WIDTH || w->proj_hidden < 1 || w->proj_hidden > EMBED_MAX_WIDTH ||
         w->embed < 1 || w->embed > EMBED_MAX_WIDTH || w->cand_hidden < 1 || w->cand_hidden > EMBED_MAX_CAND_HIDDEN || s_rows < 1 ||
         s_rows > HEAD_MAX_ROWS || n_env < 1 ||
         obs_stride < (int64_t)5 * s_rows + 9 + (int64_t)w->map_len * w->map_len || feat_stride < w->feat || row_stride < w->embed ||
-        env_stride < (int64_t)(s_rows - 1) * row_stride + w->embed || xg_stride < w->embed)
+        env_stride < (int64_t)(s_rows - 1) * row_stride + w->embed || xg_stride < w->embed ||
+        w->cand_hidden % width_step || w->cand_embed % width_step || w->proj_hidden % width_step)
         return IRBPP_ERR_ARG;
     EmbedArgs g;
     g.obs_stride = obs_stride, g.feat_stride = feat_stride, g.env_stride = env_stride, g.row_stride = row_stride, g.xg_stride = xg_stride;
@@ -1377,10 +1383,25 @@ int irbpp_embed(const irbpp_embed_weights* w, const float* obs_dev, int64_t obs_
                        w->w_conv2, w->b_conv2, w->w_conv3, w->b_conv3, w->w_p1, w->b_p1, obs_dev, shape_feat_dev, base_dev, g);
     if (hipGetLastError() != hipSuccess) return IRBPP_ERR_HIP;
     const size_t lds = (size_t)embed_rows_lds_floats(w->cand_hidden, w->cand_embed, w->proj_hidden, w->embed) * sizeof(float);
-    if (!front_rows_lds((const void*)irbpp_embed_rows_kernel, lds)) return IRBPP_ERR_HIP;
-    hipLaunchKernelGGL(irbpp_embed_rows_kernel, dim3(n_env), dim3(EMBED_ROW_THREADS), lds, (hipStream_t)stream, w->w_c1, w->b_c1,
-                       w->w_c2, w->b_c2, w->w_p1, w->w_p2, w->b_p2, obs_dev, (const float*)base_dev, x_dev, xg_dev, g);
+    if (!front_rows_lds((const void*)rows_kernel, lds)) return IRBPP_ERR_HIP;
+    hipLaunchKernelGGL(rows_kernel, dim3(n_env), dim3(EMBED_ROW_THREADS), lds, (hipStream_t)stream, w->w_c1, w->b_c1, w->w_c2,
+                       w->b_c2, w->w_p1, w->w_p2, w->b_p2, obs_dev, (const float*)base_dev, x_dev, xg_dev, g);
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+}  // extern "C++"
+
+int irbpp_embed(const irbpp_embed_weights* w, const float* obs_dev, int64_t obs_stride, const float* shape_feat_dev,
+                int64_t feat_stride, int32_t s_rows, int32_t n_env, float* base_dev, float* x_dev, int64_t env_stride,
+                int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream) {
+    return embed_launch(irbpp_embed_rows_kernel, 1, w, obs_dev, obs_stride, shape_feat_dev, feat_stride, s_rows, n_env, base_dev, x_dev,
+                        env_stride, row_stride, xg_dev, xg_stride, stream);
+}
+
+int irbpp_embed_mfma(const irbpp_embed_weights* w, const float* obs_dev, int64_t obs_stride, const float* shape_feat_dev,
+                     int64_t feat_stride, int32_t s_rows, int32_t n_env, float* base_dev, float* x_dev, int64_t env_stride,
+                     int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream) {
+    return embed_launch(irbpp_embed_rows_mfma_kernel, 4, w, obs_dev, obs_stride, shape_feat_dev, feat_stride, s_rows, n_env, base_dev,
+                        x_dev, env_stride, row_stride, xg_dev, xg_stride, stream);
 }
 
 int irbpp_order_embed(const irbpp_order_embed_weights* w, const float* obs_dev, int64_t obs_stride, const float* shape_feat_dev,

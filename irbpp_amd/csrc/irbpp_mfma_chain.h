@@ -8,7 +8,8 @@
 // This is the one place that knows the lane maps of the instruction (wave of 64 lanes, lane l, col = l & 31, half = l >> 5):
 //   A operand (32 x 2): one float per lane, A[row = col][k = half];   B operand (2 x 32): one float per lane, B[k = half][col]
 //   C / D (32 x 32):    16 floats per lane, register g is D[row = (g & 3) + 8 (g >> 2) + 4 half][col]
-// Written for reuse: irbpp_streams_mfma.hip is the first user, the row part of irbpp_embed.hip the next.
+// Written for reuse: irbpp_streams_mfma.hip is the first user, irbpp_embed_mfma.hip (the row part of the embedding stage, whose
+// chains start from a bias or from `base` and hand over through LDS) the second; tests/test_gpu_embed_mfma.py holds it too.
 // The instruction sits behind mfma_32x32x2 alone; a host build defines IRBPP_MFMA_CHAIN_SHIM and supplies
 // lockstep_mfma_32x32x2(a, b, float c[16]) in its place (tests/host/mfma_shim.h).
 #pragma once

@@ -1466,9 +1466,25 @@ def _embed_rows(state: torch.Tensor, w: EmbedWeights) -> int:
     return S
 
 
+EMBED_FORMS = ("chain", "mfma")
+
+
+def _embed_form(form: str, w: EmbedWeights) -> str:
+    """``form`` of embed's HIP path: "chain" (irbpp_embed, the fmaf chains on the vector unit) or "mfma" (irbpp_embed_mfma, the
+    three per-row layers on the matrix cores: the same bits).  "mfma" needs cand_hidden, cand_embed and proj_hidden to be
+    multiples of 4 and says so."""
+    if form not in EMBED_FORMS:
+        raise ValueError(f"embed: form must be one of {EMBED_FORMS}, not {form!r}")
+    if form == "mfma" and (w.cand_hidden % 4 or w.cand_embed % 4 or w.proj_hidden % 4):
+        raise ValueError(f"embed: form='mfma' needs cand_hidden, cand_embed and proj_hidden to be multiples of 4 "
+                         f"(cand_hidden {w.cand_hidden}, cand_embed {w.cand_embed}, proj_hidden {w.proj_hidden})")
+    return form
+
+
 @torch.no_grad()
 def embed(state: torch.Tensor, shape_feature: torch.Tensor, weights: EmbedWeights, *, use_hip: Optional[bool] = None,
-          out: Optional[torch.Tensor] = None, out_global: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+          out: Optional[torch.Tensor] = None, out_global: Optional[torch.Tensor] = None,
+          form: str = "chain") -> Tuple[torch.Tensor, torch.Tensor]:
     """The embedding stage of DQNBPP.forward without a gradient (model.py:318-326, :337-352, bufferSize == 1): the observation
     ``state`` [N, obs_len] (a slice of a wider tensor passes as it is; S follows from obs_len and ``weights.map_len``) and
     ``shape_feature`` [N, F] (shape_features' result) -> (``x`` float32 [N, S, E], ``x_global`` float32 [N, E]): the reference's
@@ -1480,8 +1496,13 @@ def embed(state: torch.Tensor, shape_feature: torch.Tensor, weights: EmbedWeight
     exactly 1 is +0.0; the mean is over all S rows in irbpp_dueling_act's summation.  On CPU tensors the exact numpy emulation
     of the definition runs, on a HIP device with ``use_hip=True`` (``None`` takes EMBED_HIP_DEFAULT) the two launches of
     irbpp_embed, else torch's layers in the same factored form (MIOpen's and rocBLAS's summation orders: close to, not
-    bit-equal with, the definition).  ``learn``'s forward with a gradient keeps torch's layers."""
+    bit-equal with, the definition).  ``learn``'s forward with a gradient keeps torch's layers.  ``form`` chooses between the
+    two row kernels of the HIP path, which give the same bits: "chain" (irbpp_embed) or "mfma" (irbpp_embed_mfma, the three
+    per-row layers on the matrix cores; cand_hidden, cand_embed and proj_hidden multiples of 4).  An unknown form and
+    "mfma" with other widths raise a ValueError on every path; the CPU emulation and torch's layers have one form and
+    otherwise ignore it."""
     w = weights
+    form = _embed_form(form, w)
     S = _embed_rows(state, w)
     N, E = int(state.shape[0]), w.embed
     dev = w.device
@@ -1497,9 +1518,10 @@ def embed(state: torch.Tensor, shape_feature: torch.Tensor, weights: EmbedWeight
         return _front_copy(*(_embed_torch(state, sf, w, S) if dev.type == "cuda" else _embed_cpu(state, sf, w, S)), out, out_global)
     from . import _lib
     ws = w._struct()
-    _lib.check(lib.irbpp_embed(C.byref(ws), _p(state), int(state.stride(0)) if N > 1 else int(state.shape[1]), _p(sf),
-                               int(sf.stride(0)) if N > 1 else w.feat, S, N, _p(w._base(N)), _p(out), env_stride, row_stride,
-                               _p(out_global), xg_stride, _stream(dev)), "irbpp_embed")
+    name = "irbpp_embed_mfma" if form == "mfma" else "irbpp_embed"
+    _lib.check(getattr(lib, name)(C.byref(ws), _p(state), int(state.stride(0)) if N > 1 else int(state.shape[1]), _p(sf),
+                                  int(sf.stride(0)) if N > 1 else w.feat, S, N, _p(w._base(N)), _p(out), env_stride, row_stride,
+                                  _p(out_global), xg_stride, _stream(dev)), name)
     return out, out_global
 
 
@@ -1507,16 +1529,16 @@ def embed(state: torch.Tensor, shape_feature: torch.Tensor, weights: EmbedWeight
 def network_greedy_action(state: torch.Tensor, points: ShapePoints, indices: torch.Tensor, shape_weights: ShapeEncoderWeights,
                           embed_weights: EmbedWeights, stream_weights: StreamWeights, support: torch.Tensor, *,
                           q_out: Optional[torch.Tensor] = None, use_hip: Optional[bool] = None,
-                          streams_form: str = "chain") -> torch.Tensor:
+                          streams_form: str = "chain", embed_form: str = "chain") -> torch.Tensor:
     """Agent.act from the observation (agent.py:51-58 with all of DQNBPP.forward, bufferSize == 1): ``state`` [N, obs_len] ->
     int64[N], the three stages chained with no torch layer in between: shape_features on the id column ``state[:, 5 S]``,
     embed, streams_greedy_action (which masks by the observation's validity flags).  ``indices``: the forward's one index set
     (``points.draw_indices``); ``q_out`` as in streams_greedy_action; ``use_hip`` is handed to all three (``None``: each
     one's own default; ``True``: the whole forward in the defined float32 arithmetic, bit for bit what the CPU form gives);
-    ``streams_form`` is streams_greedy_action's ``form``."""
+    ``streams_form`` is streams_greedy_action's ``form``, ``embed_form`` embed's."""
     S = _embed_rows(state, embed_weights)
     sf = shape_features(state[:, 5 * S], points, indices, shape_weights, use_hip=use_hip)
-    x, xg = embed(state, sf, embed_weights, use_hip=use_hip)
+    x, xg = embed(state, sf, embed_weights, use_hip=use_hip, form=embed_form)
     return streams_greedy_action(x, xg, stream_weights, support, state.to(x.device), q_out=q_out, use_hip=use_hip, form=streams_form)
 
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Tooling: the embedding stage of the network's acting forward (model.py:318-326, :337-352), three forms in one process,
+"""Tooling: the embedding stage of the network's acting forward (model.py:318-326, :337-352), four forms in one process,
 interleaved (the manner of shape_feature_rates.py):
 
     reference  the reference's lines restated on torch tensors: the heightmap CNN, init_candidate_embed, the
@@ -7,12 +7,14 @@ interleaved (the manner of shape_feature_rates.py):
     torch      replay.embed(use_hip=False): torch's layers in the factored form (project_layer[0]'s shape / map part once
                per bin, added to the candidate part of every row)
     fused      replay.embed(use_hip=True): the two launches of irbpp_embed
+    mfma       the same with form="mfma": the three per-row layers on the matrix cores (irbpp_embed_mfma), the same bits
 
     N in --bins (4096 1024: acting; 64: the no_grad forwards of learn), S = 500, L = 32, the reference's widths.
 
 Per size and form: --repeats (5) timed windows of --iters calls between device events after a warm-up, taken in turns; the
 median and the spread (max - min) of the time per call, and the multiply-adds of the factored form per millisecond of the
-fused call.  One GPU process; run it under a timeout.
+fused and of the mfma call.  Whether the two kernel forms wrote identical x and xg on the measured inputs is recorded per size
+(as bits; a NaN, which these inputs do not produce, would count as a difference).  One GPU process; run it under a timeout.
 
     python tools/embed_rates.py [--out FILE.json]
 """
@@ -70,6 +72,8 @@ def main():
             sf = torch.rand((n, FEAT), device=dev, generator=gen)
             x_out = torch.empty((n, S, w.embed), device=dev)
             xg_out = torch.empty((n, w.embed), device=dev)
+            x_mfma = torch.empty((n, S, w.embed), device=dev)
+            xg_mfma = torch.empty((n, w.embed), device=dev)
 
             def reference():
                 rows = obs[:, :5 * S].reshape(n, S, 5)
@@ -83,21 +87,31 @@ def main():
 
             forms = {"reference": reference,
                      "torch": lambda: replay.embed(obs, sf, w, use_hip=False),
-                     "fused": lambda: replay.embed(obs, sf, w, use_hip=True, out=x_out, out_global=xg_out)}
+                     "fused": lambda: replay.embed(obs, sf, w, use_hip=True, out=x_out, out_global=xg_out),
+                     "mfma": lambda: replay.embed(obs, sf, w, use_hip=True, out=x_mfma, out_global=xg_mfma, form="mfma")}
             ref = [t.clone() for t in forms["reference"]()]
             r = compare(forms, a.iters, a.repeats, warmup=2)
-            for f in ("torch", "fused"):
+            for f in ("torch", "fused", "mfma"):
                 got = forms[f]()
                 r[f]["max_abs_difference_to_reference"] = [(g - t).abs().max().item() for g, t in zip(got, ref)]
             fact, full = multiply_adds(n, S, w)
             r["multiply_adds_factored"], r["multiply_adds_reference"] = fact, full
             r["fused"]["multiply_adds_per_ms"] = fact / r["fused"]["median_ms"]
+            r["mfma"]["multiply_adds_per_ms"] = fact / r["mfma"]["median_ms"]
+            r["mfma"]["ratio_to_fused"] = r["mfma"]["median_ms"] / r["fused"]["median_ms"]
+            r["mfma"]["ratio_to_torch"] = r["mfma"]["median_ms"] / r["torch"]["median_ms"]
+            r["kernel_forms_identical"] = bool(torch.equal(x_out.view(torch.int32), x_mfma.view(torch.int32)) and
+                                               torch.equal(xg_out.view(torch.int32), xg_mfma.view(torch.int32)))
             out["bins"][f"N{n}"] = r
-            del obs, sf, x_out, xg_out, ref
+            del obs, sf, x_out, xg_out, x_mfma, xg_mfma, ref
             torch.cuda.empty_cache()
     acting = [v for k, v in out["bins"].items() if k != "N64"]
     out["fused_beats_torch_at_every_acting_size"] = bool(acting) and all(
         v["torch"]["median_ms"] - v["fused"]["median_ms"] > max(v["torch"]["spread_ms"], v["fused"]["spread_ms"]) for v in acting)
+    for name, other in (("mfma_beats_fused_at_every_acting_size", "fused"), ("mfma_beats_torch_at_every_acting_size", "torch")):
+        out[name] = bool(acting) and all(
+            v[other]["median_ms"] - v["mfma"]["median_ms"] > max(v[other]["spread_ms"], v["mfma"]["spread_ms"]) for v in acting)
+    out["kernel_forms_identical"] = all(v["kernel_forms_identical"] for v in out["bins"].values())
     text = json.dumps(out, indent=1)
     print(text)
     if a.out:
