@@ -126,6 +126,10 @@ typedef struct {
                                         tile in LDS as every other launch does (default there, on even grids with one action cell per thread:
                                         each thread reduces its own action cell's heightmap cells in registers and writes their float32 copy,
                                         no tile); identical results, for A/B runs and the parity tests                                    */
+#define IRBPP_TUNE_TRACE_PACK 33554432 /* the trace kernel packs the round records of the polygon kernel itself, one gather per round in the
+                                          wave that followed the borders (default: it dumps its point slots and a lane table once per chunk
+                                          and the polygon wave that takes a round gathers the round's positions from the dump,
+                                          irbpp_rounds.h); identical results, for A/B runs and the parity tests                            */
 #define IRBPP_TUNE_NO_SPECIALISED 1024 /* the run-time builds of the transition / emit kernels even where a build with the
                                          geometry as compile-time constants exists (16 x 16 action cells, step 2 or 4, R = 2 / 4 / 8,
                                          S = 500: BASELINE.json's configs); identical results, for A/B runs and the parity tests  */

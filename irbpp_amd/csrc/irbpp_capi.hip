@@ -219,6 +219,7 @@ int irbpp_create(const irbpp_config* cfg, irbpp_env** out) {
     P.stability = cfg->stability < 0 ? 0 : (cfg->stability > 2 ? 2 : cfg->stability);
     P.rect = (cfg->tuning & IRBPP_TUNE_RECT) ? 1 : 0;
     P.lds_tile = (cfg->tuning & IRBPP_TUNE_LDS_TILE) ? 1 : 0;
+    P.round_dump = (cfg->tuning & IRBPP_TUNE_TRACE_PACK) ? 0 : 1;
     P.wimg = P.R * (deep ? (((int)levels + 33 + 31) & ~31) : 64);   // level + 32 for levels up to `levels`, in whole words of 32 codes
     P.seg_cap = P.wide ? 64 : 2 * ((P.N + NXCD - 1) / NXCD) * P.R * P.AC;      // (the wide path hands nothing over between kernels)
     P.round_cap = P.wide ? 16 : (P.N / NXCD + 64) * 16;

@@ -32,8 +32,10 @@ constexpr int XCD_STRIDE = 64;                     // ints between the lists' co
 #ifndef IRBPP_TRACE_P
 #define IRBPP_TRACE_P 2                            // contour points per lane of a polygon round (A/B: 4 measured in profiles/r04)
 #endif
-constexpr int ROUND_POINTS = 64 * IRBPP_TRACE_P, ROUND_BYTES = ROUND_POINTS * 7;   // a round record of the polygon kernel: [points | border length | border
-                                                                     // start] per position, then the vertex-row index of the position's border
+constexpr int ROUND_POINTS = 64 * IRBPP_TRACE_P, ROUND_HDR = 16;     // a round entry of the polygon kernel: a header (irbpp_rounds.h: the entry's
+constexpr int ROUND_BYTES = ROUND_HDR + ROUND_POINTS * 7;            // form, and where a DUMP round's points lie), then, RECORD form, [points |
+                                                                     // border length | border start] per position and the vertex-row index of
+                                                                     // the position's border
 constexpr int MAX_BINS = 1 << 20;                 // bins per device (irbpp_create refuses more): keeps every per-launch index an int32
 // Height levels: floor(bin_z / resolution_z), the highest level a placement can reach (cvTools.py:78).  The tuned pipeline codes a
 // level in 6 bits (level + 32, a uint64 of present levels per rotation); configurations with more levels take the capacity path
@@ -122,8 +124,9 @@ struct State {
     uint8_t* w_imgrot;     // [N][wimg] rotation of each level image
     uint2* w_cand;         // [NXCD][seg_cap] flat lists of the launch's candidate starts, in arrival order:
                            // (bin, image<<8 | y0<<4 | x0)
-    uint8_t* w_big;        // [trace waves][TRACE_WAVE_BYTES] scratch of the sequential redo of a border with more than 128 points, then 64 x 72 spill bytes (points 56.. of the lanes' borders)
-    uint8_t* w_round;      // [NXCD][round_cap][ROUND_BYTES] round records, trace kernel -> polygon kernel
+    uint8_t* w_big;        // [trace waves][TRACE_WAVE_BYTES] scratch of the sequential redo of a border with more than 128 points, then 64 x 72 spill bytes (points 56.. of the lanes' borders),
+                           // then the dump of the wave's slots and lane table for the polygon kernel (irbpp_rounds.h)
+    uint8_t* w_round;      // [NXCD][round_cap][ROUND_BYTES] round entries (header + record), trace kernel -> polygon kernel
     int32_t* w_nround;     // [NXCD * XCD_STRIDE] records in each XCD's list
     int32_t* w_heavy;      // [2][XCD_STRIDE + heavy_cap] bins with many border starts, listed by the transition kernel for the emit kernel
                            // to serve first: counter, then the bins; two lists used in turn (StepIO::heavy_turn)
@@ -181,6 +184,8 @@ struct Params {
     int32_t rect;          // IRBPP_TUNE_RECT: isolated solid rectangles are answered by the transition kernel instead of the trace kernel (A/B)
     int32_t lds_tile;      // IRBPP_TUNE_LDS_TILE: the observe-only lattice launch stages the heightmap tile in LDS like every other launch,
                            // instead of reducing it in registers (cell_tile_stage in irbpp_kernels.hip) (A/B)
+    int32_t round_dump;    // 1: a trace wave hands its borders to the polygon kernel as a dump of its slots and the polygon wave rebuilds
+                           // the round's positions (irbpp_rounds.h); 0: the trace wave packs the round records itself
 };
 
 // ---------------------------------------------------------------------------------------------------------------------

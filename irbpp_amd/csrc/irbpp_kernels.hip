@@ -27,6 +27,7 @@
 
 #include "contours_device.h"
 #include "irbpp_device.h"
+#include "irbpp_rounds.h"
 #include "../../include/irbpp.h"
 
 // This file is compiled in TWO PASSES (it includes itself at its end): pass 1 is everything, for 256-thread workgroups; pass 2
@@ -113,30 +114,7 @@ __device__ __forceinline__ int np_floor_divide_int(double a, double b, double in
     return q;
 }
 
-// wave64 inclusive scans on the DPP network (no LDS round trips): prefix inside each row of 16 lanes by four
-// row shifts, then the row totals are carried over with the two row broadcasts.  Operands are >= 0, so the
-// 0 that a shift brings in from outside the row is the identity of both sum and max.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_shift(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xF, false); }
-__device__ __forceinline__ int wave_inclusive_sum(int v) {
-    v += dpp_shift<0x111, 0xF>(v);           // row_shr:1
-    v += dpp_shift<0x112, 0xF>(v);           // row_shr:2
-    v += dpp_shift<0x114, 0xF>(v);           // row_shr:4
-    v += dpp_shift<0x118, 0xF>(v);           // row_shr:8
-    v += dpp_shift<0x142, 0xA>(v);           // row_bcast15 into rows 1 and 3
-    v += dpp_shift<0x143, 0xC>(v);           // row_bcast31 into rows 2 and 3
-    return v;
-}
-__device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
-__device__ __forceinline__ int wave_inclusive_max(int v) {
-    v = imax(v, dpp_shift<0x111, 0xF>(v));
-    v = imax(v, dpp_shift<0x112, 0xF>(v));
-    v = imax(v, dpp_shift<0x114, 0xF>(v));
-    v = imax(v, dpp_shift<0x118, 0xF>(v));
-    v = imax(v, dpp_shift<0x142, 0xA>(v));
-    v = imax(v, dpp_shift<0x143, 0xC>(v));
-    return v;
-}
+// (the wave64 inclusive scans on the DPP network, wave_inclusive_sum / wave_inclusive_max: irbpp_rounds.h)
 
 // wave64 maximum of a float64 on the DPP network (lane 63 ends up with it; every lane gets it back by v_readlane): a
 // butterfly of __shfl_xor is six ds_bpermute_b32 per word, 24 LDS cycles each and an LDS round trip of latency per step
@@ -2161,22 +2139,10 @@ IRBPP_EMIT_WAVE_KERNEL(irbpp_emit_wave_kernel_s5, 5)
 // follows its border (trace_border), and the wave then runs approx_convex_segmented on all the closed borders,
 // 128 contour points per round; vertex bits go to the bins' rows in global memory with one atomic OR each.
 // ---------------------------------------------------------------------------------------
-#ifndef IRBPP_TRACE_SHORT
-#define IRBPP_TRACE_SHORT 0
-#endif
-constexpr int TRACE_P = IRBPP_TRACE_P;                                // contour points per lane and polygon round
-constexpr int TRACE_CAP = 128;                                        // points of a border the wave-parallel path takes
-constexpr int TRACE_LDS_CAP = 56, TRACE_SLOT = TRACE_LDS_CAP + 4;     // of which in the lane's slot in LDS (15 dwords: odd stride); the rest
-constexpr int TRACE_SPILL = TRACE_CAP - TRACE_LDS_CAP;                //   in global scratch (a border of more than 56 points: one in ~10^3)
-constexpr int TRACE_SHORT = IRBPP_TRACE_SHORT;                        // borders of up to this many points get rounds of their own, ahead of the
-                                                                      // long ones (0 = one class: measured 27.46 vs 27.25 M steps/s for 8)
-static_assert(TRACE_CAP <= 64 * TRACE_P, "a border must fit one polygon round");
-static_assert(ROUND_POINTS == 64 * TRACE_P, "a round record holds one polygon round");
-constexpr int TRACE_BIG = 768;                                        // point capacity of the sequential redo (global scratch)
+// (TRACE_P, TRACE_CAP, TRACE_LDS_CAP / TRACE_SLOT / TRACE_SPILL, TRACE_SHORT, TRACE_BIG and the carve-up of a wave's region of
+// State::w_big, TRACE_WAVE_BYTES: irbpp_rounds.h, with the two forms in which a wave's borders reach the polygon kernel)
 constexpr int TRACE_FSTRIDE = FRAME_WORDS;                            // dwords per staged image: the two frames (35: odd, lanes on distinct banks)
 static_assert(TRACE_FSTRIDE % 2 == 1 && (TRACE_SLOT / 4) % 2 == 1 && TRACE_SLOT % 4 == 0, "odd dword strides in LDS");
-constexpr int TRACE_BIG_BYTES = 6 * TRACE_BIG + 64;                   // scratch of the sequential redo: points, polygon, stack, 16-bit image
-constexpr int TRACE_WAVE_BYTES = TRACE_BIG_BYTES + 64 * TRACE_SPILL;  // per wave of the grid: the redo's scratch, then the lanes' spill bytes
 // Candidates per wave (chunk) of the trace kernel: 64 at full width; 32 or 16 when the launch has too few candidates to
 // give every SIMD a wave of 64 (a wave lasts as long as its longest border: with fewer borders per wave the mean wave is
 // shorter and the idle SIMDs take the extra waves -- launch_group in irbpp_capi.hip picks by the number of bins).
@@ -2270,29 +2236,16 @@ __device__ __forceinline__ void trace_body(const Params& P, const State& S, long
         // ---- the closed borders go to the polygon kernel in rounds of 64 * PP contour points, borders packed back
         // to back (optionally in two classes, TRACE_SHORT).  A wave traces for as long as its longest border takes and
         // has 2 to 4 rounds' worth of points: approximating them here would stretch the slowest waves, which set the
-        // kernel's duration; as records in global memory every round is one work item of irbpp_polygon_kernel.
-        auto next_round = [&](int cls, int left, int& wn, int& excl, int& base) -> unsigned long long {
-            wn = (cls == 0 ? left <= TRACE_SHORT : true) ? left : 0;
-            const int incl = wave_inclusive_sum(wn);
-            excl = incl - wn;
-            if (__builtin_amdgcn_readlane(incl, 63) == 0) return 0ull;
-            const unsigned long long todo = __ballot(wn > 0);
-            base = __builtin_amdgcn_readlane(excl, __ffsll((long long)todo) - 1);
-            return __ballot(wn > 0 && incl - base <= 64 * PP);
-        };
-        int n_rounds = 0;                                             // first pass: how many rounds
-        {
-            int left = my_n;
-            for (int cls = 0; cls < 2; ++cls)
-                for (;;) {
-                    int wn, excl, base = 0;
-                    const unsigned long long sel = next_round(cls, left, wn, excl, base);
-                    if (sel == 0ull) break;
-                    if ((sel >> lane) & 1ull) left = 0;
-                    ++n_rounds;
-                }
-        }
-        // their records: one allocation in this XCD's list (L2-local atomic, like the candidate lists)
+        // kernel's duration; as entries of a list in global memory every round is one work item of irbpp_polygon_kernel.
+        // The same goes for gathering a round's positions (a serial chain of cross-lane operations per round): the wave only
+        // COUNTS its rounds, dumps its slots and a lane table once, and leaves the gathering to the polygon wave that takes
+        // the round (irbpp_rounds.h, DUMP form).  The wave gathers itself (RECORD form) where Params::round_dump is off, for
+        // what it approximates in place, for every chunk but its first (its region of w_big holds one dump), and for a first
+        // chunk with spill bytes that a later chunk's walk would overwrite.
+        int my_round, my_start;
+        unsigned long long my_sel;
+        const int n_rounds = count_rounds(lane, my_n, my_round, my_start, my_sel);       // first pass: how many rounds, who goes where
+        // their entries: one allocation in this XCD's list (L2-local atomic, like the candidate lists)
         const int round_cap = P.round_cap;
         const int xcd = (int)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & (NXCD - 1));
         int at = 0;
@@ -2302,65 +2255,40 @@ __device__ __forceinline__ void trace_body(const Params& P, const State& S, long
         }
         const bool inline_dp = at + n_rounds > round_cap;             // list full: approximate here (never changes results)
         uint8_t* const rec0 = S.w_round + ((size_t)xcd * round_cap + at) * ROUND_BYTES;
-        int left = my_n, n_dp = 0;
-        for (int cls = 0; cls < 2; ++cls)
-        for (;;) {
-            int wn, excl, base = 0;
-            const unsigned long long sel = next_round(cls, left, wn, excl, base);
-            if (sel == 0ull) break;
-            // which border does the point at position q = u * 64 + lane belong to: border lanes drop their id at
-            // the position of their first point, a running maximum over the positions spreads it
-#pragma unroll
-            for (int u = 0; u < PP; ++u) dps[u * 64 + lane] = 0u;
-            IRBPP_WAVE_SYNC();
-            if ((sel >> lane) & 1ull) dps[excl - base] = (uint32_t)lane + 1u;
-            IRBPP_WAVE_SYNC();
-            int mark[PP];
-#pragma unroll
-            for (int u = 0; u < PP; ++u) mark[u] = (int)dps[u * 64 + lane];
-            IRBPP_WAVE_SYNC();
-            bool live[PP];
-            int pv[PP], jj[PP], nn[PP], sbq[PP], prk[PP];
-            const uint8_t* pts[PP];
-            int carry = 0;
-#pragma unroll
-            for (int u = 0; u < PP; ++u) {
-                const int run = imax(wave_inclusive_max(mark[u]), carry);
-                carry = __builtin_amdgcn_readlane(run, 63);
-                const int owner = run - 1;                                    // lane that traced this position's border
-                const int on = owner >= 0 ? owner : 0;
-                const int ns = __shfl(wn | ((excl - base) << 8), on);           // (one gather for both: wn <= 128, start < 128)
-                nn[u] = ns & 255;
-                sbq[u] = ns >> 8;
-                prk[u] = __shfl(rk, on);
-                live[u] = owner >= 0 && u * 64 + lane < sbq[u] + nn[u];
-                pts[u] = slots + on * SLOT;
-                jj[u] = u * 64 + lane - sbq[u];
-                if (!live[u]) { nn[u] = 1; sbq[u] = 0; jj[u] = 0; }
-                pv[u] = live[u] ? (int)pts[u][jj[u] < LCAP ? jj[u] : LCAP] : 0;
-                if (spilled && live[u] && jj[u] >= LCAP) pv[u] = (int)wave_spill[on * TRACE_SPILL + jj[u] - LCAP];
+        const bool dump = P.round_dump != 0 && !inline_dp && chunk == (int)blockIdx.x &&
+                          !(spilled && chunk + (int)gridDim.x < seg_first[NXCD]);
+        int n_dp = 0;
+        if (dump) {
+            if (n_rounds > 0) {
+                round_dump_store<TRACE_CPW>(lane, S.w_big + (size_t)blockIdx.x * TRACE_WAVE_BYTES, slots, my_n, rk, my_round, my_start);
+                round_headers_store(lane, rec0, n_rounds, (int)blockIdx.x, spilled, my_sel);
             }
-            if (inline_dp) {
-                approx_convex_segmented<PP>(lane, live, pv, jj, nn, sbq, pts, prk, dps, dpscratch, S.w_vmask);
-            } else {
-                uint8_t* const rec = rec0 + (size_t)n_dp * ROUND_BYTES;       // [pts | n | sb][64 * PP] bytes, then rk words
+            n_dp = n_rounds;
+        } else {
+            int left = my_n;
+            for (int cls = 0; cls < 2; ++cls)
+            for (;;) {
+                int wn, excl, base = 0;
+                const unsigned long long sel = next_round(cls, left, wn, excl, base);
+                if (sel == 0ull) break;
+                bool live[PP];
+                int pv[PP], jj[PP], nn[PP], sbq[PP], prk[PP], owner[PP];
+                round_positions<PP>(lane, sel, wn, excl - base, rk, slots, wave_spill, spilled, dps, live, pv, jj, nn, sbq, prk, owner);
+                if (inline_dp) {
+                    const uint8_t* pts[PP];
 #pragma unroll
-                for (int u = 0; u < PP; ++u) {
-                    const int q = u * 64 + lane;
-                    rec[q] = (uint8_t)pv[u];
-                    rec[64 * PP + q] = (uint8_t)(live[u] ? nn[u] : 0);         // 0: no point at this position
-                    rec[2 * 64 * PP + q] = (uint8_t)sbq[u];
-                    ((uint32_t*)(rec + 3 * 64 * PP))[q] = (uint32_t)prk[u];
+                    for (int u = 0; u < PP; ++u) pts[u] = slots + owner[u] * SLOT;
+                    approx_convex_segmented<PP>(lane, live, pv, jj, nn, sbq, pts, prk, dps, dpscratch, S.w_vmask);
+                } else {
+                    round_record_store<PP>(lane, rec0 + (size_t)n_dp * ROUND_BYTES, live, pv, nn, sbq, prk);
                 }
+                if ((sel >> lane) & 1ull) left = 0;
+                ++n_dp;
             }
-            if ((sel >> lane) & 1ull) left = 0;
-            ++n_dp;
-        }
-        if (inline_dp && n_rounds > 0 && at < round_cap) {            // reserved but unused slots of a full list: no points
-            const int lim = at + n_rounds < round_cap ? n_rounds : round_cap - at;
-            for (int i = 0; i < lim; ++i)
-#pragma unroll
-                for (int u = 0; u < PP; ++u) rec0[(size_t)i * ROUND_BYTES + 64 * PP + u * 64 + lane] = 0;
+            if (inline_dp && n_rounds > 0 && at < round_cap) {        // reserved but unused entries of a full list: no points
+                const int lim = at + n_rounds < round_cap ? n_rounds : round_cap - at;
+                for (int i = 0; i < lim; ++i) round_record_store_empty<PP>(lane, rec0 + (size_t)i * ROUND_BYTES);
+            }
         }
 #if defined(IRBPP_AB_POLY_ACCOUNT) || defined(IRBPP_AB_EMIT_ACCOUNT)
         if (false) {
@@ -2484,21 +2412,13 @@ __device__ __forceinline__ void trace_refill_body(const Params& P, const State& 
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             }
-            auto next_round = [&](int left, int& wn, int& excl, int& base) -> unsigned long long {
-                wn = left;
-                const int incl = wave_inclusive_sum(wn);
-                excl = incl - wn;
-                if (__builtin_amdgcn_readlane(incl, 63) == 0) return 0ull;
-                const unsigned long long todo = __ballot(wn > 0);
-                base = __builtin_amdgcn_readlane(excl, __ffsll((long long)todo) - 1);
-                return __ballot(wn > 0 && incl - base <= 64 * PP);
-            };
+            // (one class of borders, and always the RECORD form of irbpp_rounds.h: the slots are refilled while the rounds wait)
             int n_rounds = 0;
             {
                 int left = my_n;
                 for (;;) {
                     int wn, excl, base = 0;
-                    const unsigned long long sel = next_round(left, wn, excl, base);
+                    const unsigned long long sel = next_round(1, left, wn, excl, base);
                     if (sel == 0ull) break;
                     if ((sel >> lane) & 1ull) left = 0;
                     ++n_rounds;
@@ -2514,59 +2434,25 @@ __device__ __forceinline__ void trace_refill_body(const Params& P, const State& 
             int left = my_n, n_dp = 0;
             for (;;) {
                 int wn, excl, base = 0;
-                const unsigned long long sel = next_round(left, wn, excl, base);
+                const unsigned long long sel = next_round(1, left, wn, excl, base);
                 if (sel == 0ull) break;
-#pragma unroll
-                for (int u = 0; u < PP; ++u) dps[u * 64 + lane] = 0u;
-                IRBPP_WAVE_SYNC();
-                if ((sel >> lane) & 1ull) dps[excl - base] = (uint32_t)lane + 1u;
-                IRBPP_WAVE_SYNC();
-                int mark[PP];
-#pragma unroll
-                for (int u = 0; u < PP; ++u) mark[u] = (int)dps[u * 64 + lane];
-                IRBPP_WAVE_SYNC();
                 bool live[PP];
-                int pv[PP], jj[PP], nn[PP], sbq[PP], prk[PP];
-                const uint8_t* pts[PP];
-                int carry = 0;
-#pragma unroll
-                for (int u = 0; u < PP; ++u) {
-                    const int run = imax(wave_inclusive_max(mark[u]), carry);
-                    carry = __builtin_amdgcn_readlane(run, 63);
-                    const int owner = run - 1;
-                    const int on = owner >= 0 ? owner : 0;
-                    const int ns = __shfl(wn | ((excl - base) << 8), on);
-                    nn[u] = ns & 255;
-                    sbq[u] = ns >> 8;
-                    prk[u] = __shfl(rk, on);
-                    live[u] = owner >= 0 && u * 64 + lane < sbq[u] + nn[u];
-                    pts[u] = slots + on * SLOT;
-                    jj[u] = u * 64 + lane - sbq[u];
-                    if (!live[u]) { nn[u] = 1; sbq[u] = 0; jj[u] = 0; }
-                    pv[u] = live[u] ? (int)pts[u][jj[u] < LCAP ? jj[u] : LCAP] : 0;
-                    if (spilled && live[u] && jj[u] >= LCAP) pv[u] = (int)wave_spill[on * TRACE_SPILL + jj[u] - LCAP];
-                }
+                int pv[PP], jj[PP], nn[PP], sbq[PP], prk[PP], owner[PP];
+                round_positions<PP>(lane, sel, wn, excl - base, rk, slots, wave_spill, spilled, dps, live, pv, jj, nn, sbq, prk, owner);
                 if (inline_dp) {
+                    const uint8_t* pts[PP];
+#pragma unroll
+                    for (int u = 0; u < PP; ++u) pts[u] = slots + owner[u] * SLOT;
                     approx_convex_segmented<PP>(lane, live, pv, jj, nn, sbq, pts, prk, dps, dpscratch, S.w_vmask);
                 } else {
-                    uint8_t* const rec = rec0 + (size_t)n_dp * ROUND_BYTES;
-#pragma unroll
-                    for (int u = 0; u < PP; ++u) {
-                        const int q = u * 64 + lane;
-                        rec[q] = (uint8_t)pv[u];
-                        rec[64 * PP + q] = (uint8_t)(live[u] ? nn[u] : 0);
-                        rec[2 * 64 * PP + q] = (uint8_t)sbq[u];
-                        ((uint32_t*)(rec + 3 * 64 * PP))[q] = (uint32_t)prk[u];
-                    }
+                    round_record_store<PP>(lane, rec0 + (size_t)n_dp * ROUND_BYTES, live, pv, nn, sbq, prk);
                 }
                 if ((sel >> lane) & 1ull) left = 0;
                 ++n_dp;
             }
             if (inline_dp && n_rounds > 0 && at < round_cap) {
                 const int lim = at + n_rounds < round_cap ? n_rounds : round_cap - at;
-                for (int i = 0; i < lim; ++i)
-#pragma unroll
-                    for (int u = 0; u < PP; ++u) rec0[(size_t)i * ROUND_BYTES + 64 * PP + u * 64 + lane] = 0;
+                for (int i = 0; i < lim; ++i) round_record_store_empty<PP>(lane, rec0 + (size_t)i * ROUND_BYTES);
             }
             n_dp_total += n_dp;
             IRBPP_WAVE_SYNC();
@@ -2674,23 +2560,23 @@ irbpp_polygon_kernel(const Params P, const State S
         bool live[PP];
         int pv[PP], jj[PP], nn[PP], sbq[PP], prk[PP];
         const uint8_t* pts[PP];
-#pragma unroll
-        for (int u = 0; u < PP; ++u) {
-            const int q = u * 64 + lane;
-            pv[u] = rec[q];
-            nn[u] = rec[64 * PP + q];
-            sbq[u] = rec[2 * 64 * PP + q];
-            prk[u] = (int)((const uint32_t*)(rec + 3 * 64 * PP))[q];
-            lpts[q] = (uint8_t)pv[u];
+        // the entry's header says whether the trace wave packed the round's positions (RECORD) or left its slots and lane
+        // table in w_big for this wave to gather them (DUMP): irbpp_rounds.h
+        RoundWord4 h = *(const RoundWord4*)rec;
+        h.x = (uint32_t)__builtin_amdgcn_readfirstlane((int)h.x);
+        if (h.x & ROUND_FORM_DUMP) {
+            h.y = (uint32_t)__builtin_amdgcn_readfirstlane((int)h.y);
+            h.z = (uint32_t)__builtin_amdgcn_readfirstlane((int)h.z);
+            h.w = (uint32_t)__builtin_amdgcn_readfirstlane((int)h.w);
+            round_dump_load<PP>(lane, h, S.w_big, dps, live, pv, jj, nn, sbq, prk);
+        } else {
+            round_record_load<PP>(lane, rec, live, pv, jj, nn, sbq, prk);
         }
+#pragma unroll
+        for (int u = 0; u < PP; ++u) lpts[u * 64 + lane] = (uint8_t)pv[u];
         IRBPP_WAVE_SYNC();
 #pragma unroll
-        for (int u = 0; u < PP; ++u) {
-            live[u] = nn[u] > 0;
-            jj[u] = u * 64 + lane - sbq[u];
-            if (!live[u]) { nn[u] = 1; sbq[u] = 0; jj[u] = 0; pv[u] = 0; }
-            pts[u] = lpts + sbq[u];
-        }
+        for (int u = 0; u < PP; ++u) pts[u] = lpts + sbq[u];
 #ifdef IRBPP_AB_POLY_ACCOUNT
         const long long t_in = (long long)clock64();
         if (rounds_done == 0) t_first_loaded = t_in - t_begin;

@@ -100,8 +100,8 @@ inline bool lattice_or_box(const Params& P) { return all_block(P) || P.box != 0;
 inline bool lattice_images(const Params& P) { return P.block_b > 0 || P.box != 0; }
 
 // waves of the largest trace grid a launch over this environment's bins can ask for (16 candidates per wave: four waves per
-// bin), at most TRACE_SMALL_GRID of them beyond one per bin: State::w_big holds one scratch per wave of the grid (9 KB each:
-// a 1-bin probe environment allocates 37 KB, not 76 MB)
+// bin), at most TRACE_SMALL_GRID of them beyond one per bin: State::w_big holds one scratch per wave of the grid (13 KB each:
+// a 1-bin probe environment allocates 55 KB, not 112 MB)
 inline int trace_grid_cap(int N) {
     const int small = 4 * N < TRACE_SMALL_GRID ? 4 * N : TRACE_SMALL_GRID;
     return N > small ? N : small;
