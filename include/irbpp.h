@@ -824,6 +824,20 @@ int irbpp_order_embed(const irbpp_order_embed_weights* w, const float* obs_dev, 
                       int32_t k_slots, int32_t n_env, float* base_dev /* workspace [n_env][proj_hidden] */,
                       float* x_dev, int64_t env_stride, int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream);
 
+/* irbpp_order_embed with its eight linear layers (both of gat_project_layer, W_query, W_key, W_val, W_out and the
+ * feed-forward pair) on the matrix cores (csrc/irbpp_order_embed_mfma.hip, csrc/irbpp_mfma_chain.h): the same arguments,
+ * workspace, outputs and definition, two launches on `stream` (irbpp_order_embed's own bin kernel, then the row kernel of this
+ * form); the k x k attention between the layers stays on the vector unit.  The float32 matrix instruction of gfx950 rounds
+ * once per product and accumulates in k order, so with the accumulator started from the chain's start (base of the row's
+ * bin, a bias, +0.0), the k-steps issued ascending and each residual added after its chain every output is the chain of the
+ * definition: x and xg equal irbpp_order_embed's bit for bit wherever irbpp_order_embed's are not NaN.  Same limits and
+ * status codes, and feat % 4 == 0, proj_hidden % 4 == 0, embed % 4 == 0 and ff_hidden % 4 == 0 (the k of the eight products
+ * is never padded): IRBPP_ERR_ARG otherwise, never another form in its place. */
+int irbpp_order_embed_mfma(const irbpp_order_embed_weights* w, const float* obs_dev, int64_t obs_stride,
+                           const float* shape_feat_dev, int64_t feat_stride /* between (bin, slot) rows */,
+                           int32_t k_slots, int32_t n_env, float* base_dev /* workspace [n_env][proj_hidden] */,
+                           float* x_dev, int64_t env_stride, int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream);
+
 /* One parameter tensor of the optimiser step: float32, contiguous, numel elements, 4-byte alignment is enough (16-byte
  * aligned bases take 16-byte accesses).  target may be NULL (nothing is copied for that tensor). */
 typedef struct { float *param, *grad, *exp_avg, *exp_avg_sq, *target; int64_t numel; } irbpp_optim_tensor;

@@ -33,6 +33,7 @@
 #include "irbpp_embed.hip"          // the embedding stage: heightmap CNN, candidate rows, masked mean (irbpp_embed)
 #include "irbpp_embed_mfma.hip"     // the same stage with the three per-row layers on the matrix cores, the same bits (irbpp_embed_mfma)
 #include "irbpp_order_embed.hip"   // the order network's embedding stage: CNN, k buffered items, one attention layer, mean (irbpp_order_embed)
+#include "irbpp_order_embed_mfma.hip"   // the same stage with its eight linear layers on the matrix cores, the same bits (irbpp_order_embed_mfma)
 #include "irbpp_metrics.hip"        // the trainer's episode metrics (irbpp_set_episode_window)
 #include "irbpp_itemgen.h"
 #include "irbpp_plan.h"             // which kernels a transition launches: the registry of kernels and plan_transition
@@ -1405,15 +1406,20 @@ int irbpp_embed_mfma(const irbpp_embed_weights* w, const float* obs_dev, int64_t
                         x_dev, env_stride, row_stride, xg_dev, xg_stride, stream);
 }
 
-int irbpp_order_embed(const irbpp_order_embed_weights* w, const float* obs_dev, int64_t obs_stride, const float* shape_feat_dev,
-                      int64_t feat_stride, int32_t k_slots, int32_t n_env, float* base_dev, float* x_dev, int64_t env_stride,
-                      int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream) {
+// the two forms of the order network's embedding stage: the bin kernel, then `rows_kernel` (irbpp_order_rows_kernel or its MFMA
+// form, which needs the K of its eight products, width_step = 4, never padded) with `lds` bytes of dynamic LDS
+extern "C++" {
+template <typename K>
+static int order_embed_launch(K rows_kernel, int width_step, const irbpp_order_embed_weights* w, const float* obs_dev, int64_t obs_stride,
+                              const float* shape_feat_dev, int64_t feat_stride, int32_t k_slots, int32_t n_env, float* base_dev,
+                              float* x_dev, int64_t env_stride, int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream) {
     if (!w || front_encoder_bad(w) || !w->w_g1 || !w->b_g1 || !w->w_g2 || !w->b_g2 || !w->w_q || !w->w_k || !w->w_v || !w->w_o ||
         !w->b_o || !w->w_f1 || !w->b_f1 || !w->w_f2 || !w->b_f2 || !obs_dev || !shape_feat_dev || !base_dev || !x_dev || !xg_dev ||
         w->feat < 1 || w->feat > ORDER_MAX_WIDTH || w->proj_hidden < 1 || w->proj_hidden > ORDER_MAX_WIDTH || w->embed < 1 ||
         w->embed > ORDER_MAX_WIDTH || w->ff_hidden < 1 || w->ff_hidden > ORDER_MAX_WIDTH || k_slots < 2 || k_slots > ORDER_MAX_SLOTS ||
         n_env < 1 || obs_stride < (int64_t)k_slots + (int64_t)w->map_len * w->map_len || feat_stride < w->feat ||
-        row_stride < w->embed || env_stride < (int64_t)(k_slots - 1) * row_stride + w->embed || xg_stride < w->embed)
+        row_stride < w->embed || env_stride < (int64_t)(k_slots - 1) * row_stride + w->embed || xg_stride < w->embed ||
+        w->feat % width_step || w->proj_hidden % width_step || w->embed % width_step || w->ff_hidden % width_step)
         return IRBPP_ERR_ARG;
     OrderEmbedArgs g;
     g.obs_stride = obs_stride, g.feat_stride = feat_stride, g.env_stride = env_stride, g.row_stride = row_stride, g.xg_stride = xg_stride;
@@ -1423,12 +1429,29 @@ int irbpp_order_embed(const irbpp_order_embed_weights* w, const float* obs_dev, 
     hipLaunchKernelGGL(irbpp_order_bin_kernel, dim3(n_env), dim3(EMBED_BIN_THREADS), 0, (hipStream_t)stream, w->w_conv1, w->b_conv1,
                        w->w_conv2, w->b_conv2, w->w_conv3, w->b_conv3, w->w_g1, w->b_g1, obs_dev, base_dev, g);
     if (hipGetLastError() != hipSuccess) return IRBPP_ERR_HIP;
-    const size_t lds = (size_t)order_rows_lds_floats(w->feat, w->proj_hidden, w->embed, w->ff_hidden, k_slots) * sizeof(float);
-    if (!front_rows_lds((const void*)irbpp_order_rows_kernel, lds)) return IRBPP_ERR_HIP;
-    hipLaunchKernelGGL(irbpp_order_rows_kernel, dim3(order_tiles(n_env, k_slots)), dim3(EMBED_ROW_THREADS), lds, (hipStream_t)stream,
+    const int lds_floats = width_step == 1 ? order_rows_lds_floats(w->feat, w->proj_hidden, w->embed, w->ff_hidden, k_slots)
+                                           : order_rows_mfma_lds_floats(w->feat, w->proj_hidden, w->embed, w->ff_hidden, k_slots);
+    const size_t lds = (size_t)lds_floats * sizeof(float);
+    if (!front_rows_lds((const void*)rows_kernel, lds)) return IRBPP_ERR_HIP;
+    hipLaunchKernelGGL(rows_kernel, dim3(order_tiles(n_env, k_slots)), dim3(EMBED_ROW_THREADS), lds, (hipStream_t)stream,
                        w->w_g1, w->w_g2, w->b_g2, w->w_q, w->w_k, w->w_v, w->w_o, w->b_o, w->w_f1, w->b_f1, w->w_f2, w->b_f2,
                        shape_feat_dev, (const float*)base_dev, x_dev, xg_dev, g);
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+}  // extern "C++"
+
+int irbpp_order_embed(const irbpp_order_embed_weights* w, const float* obs_dev, int64_t obs_stride, const float* shape_feat_dev,
+                      int64_t feat_stride, int32_t k_slots, int32_t n_env, float* base_dev, float* x_dev, int64_t env_stride,
+                      int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream) {
+    return order_embed_launch(irbpp_order_rows_kernel, 1, w, obs_dev, obs_stride, shape_feat_dev, feat_stride, k_slots, n_env, base_dev,
+                              x_dev, env_stride, row_stride, xg_dev, xg_stride, stream);
+}
+
+int irbpp_order_embed_mfma(const irbpp_order_embed_weights* w, const float* obs_dev, int64_t obs_stride, const float* shape_feat_dev,
+                           int64_t feat_stride, int32_t k_slots, int32_t n_env, float* base_dev, float* x_dev, int64_t env_stride,
+                           int64_t row_stride, float* xg_dev, int64_t xg_stride, void* stream) {
+    return order_embed_launch(irbpp_order_rows_mfma_kernel, 4, w, obs_dev, obs_stride, shape_feat_dev, feat_stride, k_slots, n_env,
+                              base_dev, x_dev, env_stride, row_stride, xg_dev, xg_stride, stream);
 }
 
 int irbpp_replay_gather(const irbpp_replay_view* v, int32_t draws, float beta, const int64_t* data_idx_dev, const float* prob_dev,

@@ -10,6 +10,8 @@
 //   C / D (32 x 32):    16 floats per lane, register g is D[row = (g & 3) + 8 (g >> 2) + 4 half][col]
 // Written for reuse: irbpp_streams_mfma.hip is the first user, irbpp_embed_mfma.hip (the row part of the embedding stage, whose
 // chains start from a bias or from `base` and hand over through LDS) the second; tests/test_gpu_embed_mfma.py holds it too.
+// irbpp_order_embed_mfma.hip (the order network's eight layers: chains started from a `base` per column, from a bias and from
+// +0.0) is the third, held by tests/test_gpu_order_embed_mfma.py.
 // The instruction sits behind mfma_32x32x2 alone; a host build defines IRBPP_MFMA_CHAIN_SHIM and supplies
 // lockstep_mfma_32x32x2(a, b, float c[16]) in its place (tests/host/mfma_shim.h).
 #pragma once
@@ -60,6 +62,22 @@ __device__ __forceinline__ void mfma_chain_bias(MfmaAcc& c, const float* __restr
         const int i = row0 + mfma_acc_row(g, half);
         c.r[g] = bias[i < rows ? i : rows - 1];
     }
+}
+
+// C = a start of its own per column (a lane holds one column of the tile): row i of the lane's column starts its chain from
+// start_col[row0 + i], start_col the lane's own pointer; rows at or past `rows` take the last one that exists (thrown away)
+__device__ __forceinline__ void mfma_chain_col_start(MfmaAcc& c, const float* start_col, int row0, int rows, int half) {
+#pragma unroll
+    for (int g = 0; g < MFMA_ACC; ++g) {
+        const int i = row0 + mfma_acc_row(g, half);
+        c.r[g] = start_col[i < rows ? i : rows - 1];
+    }
+}
+
+// C = +0.0: chains without a bias
+__device__ __forceinline__ void mfma_chain_zero(MfmaAcc& c) {
+#pragma unroll
+    for (int g = 0; g < MFMA_ACC; ++g) c.r[g] = 0.0f;
 }
 
 // four steps of k, ascending, as two instructions: a4 = A[col][k .. k + 3] and b4 = B[k .. k + 3][col], the same four in

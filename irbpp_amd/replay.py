@@ -1549,7 +1549,9 @@ def network_greedy_action(state: torch.Tensor, points: ShapePoints, indices: tor
 # at both (profiles/order_embed/).  The reference's lines with their host gather: 135 and 27 ms.  Measured for the stage from
 # a given shape feature; the whole acting forward: 1.04 / 0.73 ms with every stage's default, 4.78 / 1.38 ms with
 # use_hip=True throughout (irbpp_streams_act is most of that).  Not measured: other k, and bins below 1024.
-# use_hip=True asks for the kernels (the reproducible forward).
+# use_hip=True asks for the kernels (the reproducible forward).  form="mfma" (the eight linear layers on the matrix cores, the
+# same bits) measured in a later run of the same tool: 0.825 ms against 1.197 (chain) and 0.821 (torch) at 4096 bins, 0.254
+# against 0.394 and 0.523 at 1024: level with torch's layers at 4096, not beyond the spread, so the rule is still not met.
 ORDER_EMBED_HIP_DEFAULT = False
 
 ORDER_MAX_WIDTH, ORDER_MAX_SLOTS = 256, 64
@@ -1676,9 +1678,25 @@ def _order_slots(state: torch.Tensor, w: OrderEmbedWeights) -> int:
     return k
 
 
+ORDER_EMBED_FORMS = ("chain", "mfma")
+
+
+def _order_embed_form(form: str, w: "OrderEmbedWeights") -> str:
+    """``form`` of order_embed's HIP path: "chain" (irbpp_order_embed, the fmaf chains on the vector unit) or "mfma"
+    (irbpp_order_embed_mfma, the eight linear layers on the matrix cores: the same bits).  "mfma" needs feat, proj_hidden, embed
+    and ff_hidden to be multiples of 4 and says so."""
+    if form not in ORDER_EMBED_FORMS:
+        raise ValueError(f"order_embed: form must be one of {ORDER_EMBED_FORMS}, not {form!r}")
+    if form == "mfma" and (w.feat % 4 or w.proj_hidden % 4 or w.embed % 4 or w.ff_hidden % 4):
+        raise ValueError(f"order_embed: form='mfma' needs feat, proj_hidden, embed and ff_hidden to be multiples of 4 "
+                         f"(feat {w.feat}, proj_hidden {w.proj_hidden}, embed {w.embed}, ff_hidden {w.ff_hidden})")
+    return form
+
+
 @torch.no_grad()
 def order_embed(state: torch.Tensor, shape_feature: torch.Tensor, weights: OrderEmbedWeights, *, use_hip: Optional[bool] = None,
-                out: Optional[torch.Tensor] = None, out_global: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                out: Optional[torch.Tensor] = None, out_global: Optional[torch.Tensor] = None,
+                form: str = "chain") -> Tuple[torch.Tensor, torch.Tensor]:
     """The embedding stage of the order network, DQNBPP.forward without a gradient for bufferSize > 1 (model.py:355-383): the
     order observation ``state`` [N, k + L^2] (k buffered item ids, then the heightmap; a slice of a wider tensor passes as it
     is; k follows from obs_len and ``weights.map_len``) and ``shape_feature`` [N*k, F] or [N, k, F] (shape_features over the
@@ -1689,8 +1707,13 @@ def order_embed(state: torch.Tensor, shape_feature: torch.Tensor, weights: Order
     concatenation order; one attention head without a mask, its softmax with irbpp_dueling_act's exp; the mean in its
     summation.  On CPU tensors the exact numpy emulation of the definition runs, on a HIP device with ``use_hip=True``
     (``None`` takes ORDER_EMBED_HIP_DEFAULT) the two launches of irbpp_order_embed, else torch's layers in the same factored
-    form (close to, not bit-equal with, the definition).  ``learn``'s forward with a gradient keeps torch's layers."""
+    form (close to, not bit-equal with, the definition).  ``learn``'s forward with a gradient keeps torch's layers.  ``form``
+    chooses between the two row kernels of the HIP path, which give the same bits: "chain" (irbpp_order_embed) or "mfma"
+    (irbpp_order_embed_mfma, the eight linear layers on the matrix cores; feat, proj_hidden, embed and ff_hidden multiples of
+    4).  An unknown form and "mfma" with other widths raise a ValueError on every path; the CPU emulation and torch's layers
+    have one form and otherwise ignore it."""
     w = weights
+    form = _order_embed_form(form, w)
     k = _order_slots(state, w)
     N, E, F_ = int(state.shape[0]), w.embed, w.feat
     dev = w.device
@@ -1709,9 +1732,10 @@ def order_embed(state: torch.Tensor, shape_feature: torch.Tensor, weights: Order
         return _front_copy(*(_order_embed_torch(state, sf, w, k) if dev.type == "cuda" else _order_embed_cpu(state, sf, w, k)), out, out_global)
     from . import _lib
     ws = w._struct()
-    _lib.check(lib.irbpp_order_embed(C.byref(ws), _p(state), int(state.stride(0)) if N > 1 else int(state.shape[1]), _p(sf),
-                                     int(sf.stride(0)), k, N, _p(w._base(N)), _p(out), env_stride, row_stride, _p(out_global),
-                                     xg_stride, _stream(dev)), "irbpp_order_embed")
+    name = "irbpp_order_embed_mfma" if form == "mfma" else "irbpp_order_embed"
+    _lib.check(getattr(lib, name)(C.byref(ws), _p(state), int(state.stride(0)) if N > 1 else int(state.shape[1]), _p(sf),
+                                  int(sf.stride(0)), k, N, _p(w._base(N)), _p(out), env_stride, row_stride, _p(out_global),
+                                  xg_stride, _stream(dev)), name)
     return out, out_global
 
 
@@ -1719,17 +1743,18 @@ def order_embed(state: torch.Tensor, shape_feature: torch.Tensor, weights: Order
 def order_network_greedy_action(state: torch.Tensor, points: ShapePoints, indices: torch.Tensor, shape_weights: ShapeEncoderWeights,
                                 order_weights: OrderEmbedWeights, stream_weights: StreamWeights, support: torch.Tensor, *,
                                 q_out: Optional[torch.Tensor] = None, use_hip: Optional[bool] = None,
-                                streams_form: str = "chain") -> torch.Tensor:
+                                streams_form: str = "chain", order_form: str = "chain") -> torch.Tensor:
     """The order network's Agent.act from the observation (``orderDQN.act(orderState, None)``, trainer.py:266, with all of
     DQNBPP.forward for bufferSize > 1): ``state`` [N, k + L^2] -> int64[N] in [0, k), the three stages chained with no torch
     layer in between: shape_features on the N k ids ``state[:, :k]`` (one small strided copy makes them contiguous), order_embed,
     streams_greedy_action without a mask.  ``indices``, ``q_out`` and ``use_hip`` as in network_greedy_action (``True``: the
     whole forward in the defined float32 arithmetic, bit for bit what the CPU form gives: on CPU tensors the head is a numpy
     emulation of irbpp_dueling_act, not streams_greedy_action's torch lines); ``streams_form`` is streams_greedy_action's
-    ``form``."""
+    ``form``, ``order_form`` order_embed's."""
+    order_form = _order_embed_form(order_form, order_weights)
     k = _order_slots(state, order_weights)
     sf = shape_features(state[:, :k].contiguous(), points, indices, shape_weights, use_hip=use_hip)
-    x, xg = order_embed(state, sf, order_weights, use_hip=use_hip)
+    x, xg = order_embed(state, sf, order_weights, use_hip=use_hip, form=order_form)
     if x.is_cuda:
         return streams_greedy_action(x, xg, stream_weights, support, None, q_out=q_out, use_hip=use_hip, form=streams_form)
     # the CPU form stays in the defined arithmetic to the end (streams_greedy_action's CPU form ends in torch's softmax)

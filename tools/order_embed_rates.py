@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Tooling: the order network's embedding stage (model.py:355-383, bufferSize > 1), three forms in one process, interleaved
+"""Tooling: the order network's embedding stage (model.py:355-383, bufferSize > 1), four forms in one process, interleaved
 (the manner of embed_rates.py):
 
     reference  the reference's lines restated on torch tensors: the heightmap CNN, shapeArray[ids.cpu()] on the host with the
@@ -9,14 +9,16 @@
                the reference's stage comes)
     torch      replay.order_embed(use_hip=False): torch's layers in the factored form, from a given shape feature
     fused      replay.order_embed(use_hip=True): the two launches of irbpp_order_embed, from a given shape feature
+    mfma       the same with form="mfma": the eight linear layers on the matrix cores (irbpp_order_embed_mfma), the same bits
 
-and the same three for the whole acting forward (order_network_greedy_action with use_hip=True / None, and the reference's
+and the first three for the whole acting forward (order_network_greedy_action with use_hip=True / None, and the reference's
 lines followed by torch's streams, softmax and arg-max), as "chain_*".
 
     N in --bins (4096 1024), k = 10 (cfg 4), L = 32, the reference's widths, 100 shapes of 1000 points, 256 sampled.
 
 Per size and form: --repeats (5) timed windows of --iters calls between device events after a warm-up, taken in turns; the
-median and the spread (max - min) of the time per call.  One GPU process; run it under a timeout.
+median and the spread (max - min) of the time per call.  Whether the two kernel forms wrote identical x and xg on the measured
+inputs is recorded per size ("kernel_forms_identical").  One GPU process; run it under a timeout.
 
     python tools/order_embed_rates.py [--out FILE.json]
 """
@@ -89,6 +91,8 @@ def main():
             sf = replay.shape_features(obs[:, :K].contiguous(), points, indices, sw, use_hip=True)
             x_out = torch.empty((n, K, E), device=dev)
             xg_out = torch.empty((n, E), device=dev)
+            x_mfma = torch.empty((n, K, E), device=dev)
+            xg_mfma = torch.empty((n, E), device=dev)
 
             def reference():
                 fmap = height(obs[:, K:].reshape(n, 1, L, L)).reshape(n, -1)
@@ -119,20 +123,29 @@ def main():
             forms = {"reference": reference,
                      "torch": lambda: replay.order_embed(obs, sf, w, use_hip=False),
                      "fused": lambda: replay.order_embed(obs, sf, w, use_hip=True, out=x_out, out_global=xg_out),
+                     "mfma": lambda: replay.order_embed(obs, sf, w, use_hip=True, out=x_mfma, out_global=xg_mfma, form="mfma"),
                      "chain_reference": chain_reference,
                      "chain_default": lambda: (replay.order_network_greedy_action(obs, points, indices, sw, w, tw, support),),
                      "chain_fused": lambda: (replay.order_network_greedy_action(obs, points, indices, sw, w, tw, support, use_hip=True),)}
             ref = [t.clone() for t in forms["reference"]()]
             r = compare(forms, a.iters, a.repeats, warmup=2)
-            for f in ("torch", "fused"):
+            for f in ("torch", "fused", "mfma"):
                 got = forms[f]()
                 r[f]["max_abs_difference_to_reference"] = [(g - t).abs().max().item() for g, t in zip(got, ref)]
+            r["mfma"]["ratio_to_fused"] = r["mfma"]["median_ms"] / r["fused"]["median_ms"]
+            r["mfma"]["ratio_to_torch"] = r["mfma"]["median_ms"] / r["torch"]["median_ms"]
+            r["kernel_forms_identical"] = bool(torch.equal(x_out.view(torch.int32), x_mfma.view(torch.int32)) and
+                                               torch.equal(xg_out.view(torch.int32), xg_mfma.view(torch.int32)))
             out["bins"][f"N{n}"] = r
-            del obs, sf, x_out, xg_out, ref
+            del obs, sf, x_out, xg_out, x_mfma, xg_mfma, ref
             torch.cuda.empty_cache()
     sizes = list(out["bins"].values())
     out["fused_beats_torch_at_every_size"] = bool(sizes) and all(
         v["torch"]["median_ms"] - v["fused"]["median_ms"] > max(v["torch"]["spread_ms"], v["fused"]["spread_ms"]) for v in sizes)
+    for name, other in (("mfma_beats_fused_at_every_size", "fused"), ("mfma_beats_torch_at_every_size", "torch")):
+        out[name] = bool(sizes) and all(
+            v[other]["median_ms"] - v["mfma"]["median_ms"] > max(v[other]["spread_ms"], v["mfma"]["spread_ms"]) for v in sizes)
+    out["kernel_forms_identical"] = all(v["kernel_forms_identical"] for v in sizes)
     text = json.dumps(out, indent=1)
     print(text)
     if a.out:
