@@ -892,6 +892,20 @@ int irbpp_debug_kernel_timing(irbpp_env* env, int32_t capacity);
  * 0.15 ms per step, so bench.py samples every fourth step of its timed region */
 int irbpp_debug_kernel_timing_every(irbpp_env* env, int32_t every);
 int irbpp_debug_kernel_times(irbpp_env* env, float* ms_host, int32_t max_count, int32_t* count);
+/* Tooling: shrink the capacity of the eight per-die lists of polygon rounds (trace kernel -> polygon kernel), so that a FULL
+ * list -- trace waves that approximate their borders in place, empty entries below the cap, the polygon kernel's clamp -- can
+ * be reached with a handful of bins.  1 <= cap <= the capacity irbpp_create computed ((num_bins / 8 + 64) * 16); the
+ * allocation stays as it is and both kernels index the lists with the cap as their stride.  IRBPP_ERR_ARG outside that range
+ * and on the wide path (which has no such lists); IRBPP_ERR_STATE once a transition has been launched: one stride for the
+ * environment's whole life keeps every stale entry a well-formed record of an earlier observation (the memory starts zeroed,
+ * which reads as empty records).  Results never depend on the cap. */
+int irbpp_debug_round_cap(irbpp_env* env, int32_t cap);
+/* Tooling: the eight lists' reservation totals of the last observing launch to out[0..7] on the host: every trace wave adds
+ * its rounds to its die's counter whether they fit or not, so a total above the cap says that list was full.  The emit kernel
+ * that ends an observation retires the counters, so they are copied on the stream right behind the trace kernel -- from the
+ * FIRST call of this function on, which switches that copy on (and answers zeros, like every call before a launch).
+ * Synchronises the stream.  IRBPP_ERR_ARG on the wide path. */
+int irbpp_debug_round_counts(irbpp_env* env, int32_t out[8], void* stream);
 
 /* Device-side error word raised by kernels (0 = none).  Synchronises the stream. */
 int irbpp_device_error(irbpp_env* env, void* stream, int32_t* flags_out);

@@ -184,6 +184,8 @@ SIGNATURES = {
     "irbpp_debug_kernel_timing": (C.c_int, [C.c_void_p, C.c_int32]),
     "irbpp_debug_kernel_timing_every": (C.c_int, [C.c_void_p, C.c_int32]),
     "irbpp_debug_kernel_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32)]),
+    "irbpp_debug_round_cap": (C.c_int, [C.c_void_p, C.c_int32]),
+    "irbpp_debug_round_counts": (C.c_int, [C.c_void_p, c_i32_p, C.c_void_p]),
     "irbpp_device_error": (C.c_int, [C.c_void_p, C.c_void_p, c_i32_p]),
 }
 

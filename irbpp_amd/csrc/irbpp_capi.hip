@@ -47,6 +47,9 @@ struct irbpp_env {
     Tables T;
     State S;
     bool shapes_loaded = false, seq_loaded = false, was_reset = false;
+    bool transition_launched = false;      // launch_env went out at least once (irbpp_debug_round_cap is refused from then on)
+    int32_t round_cap_alloc = 0;           // Params::round_cap as irbpp_create computed it: what State::w_round was allocated for
+    int32_t* round_snap = nullptr;         // irbpp_debug_round_counts: State::w_nround as the trace kernel left it (null: not recorded)
     bool item_order = false;               // launch slots grouped by observed item, one contiguous range per XCD (generic path)
     long long* phase_cycles = nullptr;
     int32_t* auto_actions = nullptr;       // irbpp_set_auto_policy
@@ -224,6 +227,7 @@ int irbpp_create(const irbpp_config* cfg, irbpp_env** out) {
     P.wimg = P.R * (deep ? (((int)levels + 33 + 31) & ~31) : 64);   // level + 32 for levels up to `levels`, in whole words of 32 codes
     P.seg_cap = P.wide ? 64 : 2 * ((P.N + NXCD - 1) / NXCD) * P.R * P.AC;      // (the wide path hands nothing over between kernels)
     P.round_cap = P.wide ? 16 : (P.N / NXCD + 64) * 16;
+    env->round_cap_alloc = P.round_cap;
     layout_lds_host(P);                 // redone by irbpp_load_shapes if the block path applies
     if (P.lds_bytes_full > 160 * 1024 || (P.wide && wide_layout(P).bytes > 160 * 1024)) { delete env; return IRBPP_ERR_ARG; }
 
@@ -576,6 +580,9 @@ static void launch_group(irbpp_env* env, StepIO io, const Plan& plan, int32_t* r
                 Params Pt = env->P;
                 if (plan.inline_polygon) Pt.round_cap = 0;
                 hipLaunchKernelGGL((trace_kernel_fn)fn, dim3(l.grid), dim3(l.block), l.lds, st, Pt, env->S, env->phase_cycles);
+                if (env->round_snap)     // tooling: the emit kernel behind it retires the counters, so they are copied here
+                    (void)hipMemcpyAsync(env->round_snap, env->S.w_nround, NXCD * XCD_STRIDE * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
+                                         // (an error is sticky: launch_env's hipGetLastError reports it, as for the launches)
                 break;
             }
             case K_POLYGON:
@@ -620,6 +627,7 @@ static bool graph_wanted(const irbpp_env* env, int) { return (env->cfg.tuning & 
 static int launch_env(irbpp_env* env, StepIO io, int mode, void* stream, int grid = 0, int key = KEY_CAND) {
     if (grid <= 0) grid = env->P.N;
     if (key == KEY_HEUR && grid != env->P.N) return IRBPP_ERR_ARG;     // (HM's scorer covers all bins: plan_transition)
+    env->transition_launched = true;
     io.phase_cycles = env->phase_cycles;
     hipStream_t st = (hipStream_t)stream;
     size_t pairs = env->timing.size() / 2;
@@ -1611,6 +1619,30 @@ int irbpp_debug_kernel_times(irbpp_env* env, float* ms_host, int32_t max_count, 
     }
     *count = (int32_t)n;
     env->timing_next = env->timing_used = 0;
+    return IRBPP_OK;
+}
+
+int irbpp_debug_round_cap(irbpp_env* env, int32_t cap) {
+    if (!env || env->P.wide || cap < 1 || cap > env->round_cap_alloc) return IRBPP_ERR_ARG;
+    if (env->transition_launched) return IRBPP_ERR_STATE;       // (one stride for the lists' whole life: irbpp.h)
+    drop_graphs(env);
+    env->P.round_cap = cap;
+    return IRBPP_OK;
+}
+
+int irbpp_debug_round_counts(irbpp_env* env, int32_t out[8], void* stream) {
+    static_assert(NXCD == 8, "irbpp.h documents eight lists");
+    if (!env || !out || env->P.wide) return IRBPP_ERR_ARG;
+    if (env->round_snap == nullptr) {                           // the first call switches the recording on
+        HIP_TRY(hipSetDevice(env->cfg.device));
+        drop_graphs(env);                                       // (a captured chain has no copy node yet)
+        const int rc = dev_alloc(env, &env->round_snap, NXCD * XCD_STRIDE);
+        if (rc != IRBPP_OK) { env->round_snap = nullptr; return rc; }
+    }
+    int32_t words[NXCD * XCD_STRIDE];
+    HIP_TRY(hipMemcpyAsync(words, env->round_snap, sizeof words, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    for (int s = 0; s < NXCD; ++s) out[s] = words[s * XCD_STRIDE];
     return IRBPP_OK;
 }
 

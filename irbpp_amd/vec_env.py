@@ -438,6 +438,21 @@ class GpuPackingEnv(object):
         _lib.check(self.lib.irbpp_debug_kernel_times(self._h, buf, cap, C.byref(n)), "irbpp_debug_kernel_times")
         return np.array(buf[:n.value], dtype=np.float64)
 
+    def debug_round_cap(self, cap: int) -> None:
+        """Tooling: shrink the capacity of the eight per-die lists of polygon rounds to ``cap`` entries each (at most what the
+        environment was created with), before the first reset: a full list then occurs with a handful of bins.  Results
+        never depend on it."""
+        _lib.check(self.lib.irbpp_debug_round_cap(self._h, int(cap)), "irbpp_debug_round_cap")
+
+    def debug_round_counts(self) -> np.ndarray:
+        """Tooling: int32[8], the rounds the trace waves of the last observing launch reserved in each die's list, whether
+        they fitted or not (a count above the capacity: that list was full).  The first call switches the recording on and
+        answers zeros: call it once before the launches whose counts are wanted.  Synchronises the current stream."""
+        out = np.zeros(8, dtype=np.int32)
+        _lib.check(self.lib.irbpp_debug_round_counts(self._h, out.ctypes.data_as(_lib.c_i32_p), self._stream()),
+                   "irbpp_debug_round_counts")
+        return out
+
     def check_device_error(self) -> None:
         flags = C.c_int32(0)
         _lib.check(self.lib.irbpp_device_error(self._h, self._stream(), C.byref(flags)),

@@ -1,7 +1,7 @@
 """Polygon rounds as a DUMP of the trace wave's slots (csrc/irbpp_rounds.h; the default) against the RECORD form, in which the
 trace wave packs every round itself (IRBPP_TUNE_TRACE_PACK): byte-identical observations, next actions of the scripted policy
-and step infos, step for step, and both equal to the C oracle.  (A full round list has no device coverage here -- the library
-offers no way to shrink Params::round_cap from Python; tests/test_round_dump_on_host.py covers the routines it shares.)"""
+and step infos, step for step, and both equal to the C oracle.  (A FULL round list runs on the device in
+tests/test_gpu_round_list_full.py, with Params::round_cap shrunk; tests/test_round_dump_on_host.py covers the routines it shares.)"""
 import numpy as np
 import pytest
 import torch
