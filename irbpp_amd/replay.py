@@ -1529,17 +1529,19 @@ def embed(state: torch.Tensor, shape_feature: torch.Tensor, weights: EmbedWeight
 def network_greedy_action(state: torch.Tensor, points: ShapePoints, indices: torch.Tensor, shape_weights: ShapeEncoderWeights,
                           embed_weights: EmbedWeights, stream_weights: StreamWeights, support: torch.Tensor, *,
                           q_out: Optional[torch.Tensor] = None, use_hip: Optional[bool] = None,
-                          streams_form: str = "chain", embed_form: str = "chain") -> torch.Tensor:
+                          streams_form: str = "chain", embed_form: str = "chain", mask: bool = True) -> torch.Tensor:
     """Agent.act from the observation (agent.py:51-58 with all of DQNBPP.forward, bufferSize == 1): ``state`` [N, obs_len] ->
     int64[N], the three stages chained with no torch layer in between: shape_features on the id column ``state[:, 5 S]``,
-    embed, streams_greedy_action (which masks by the observation's validity flags).  ``indices``: the forward's one index set
+    embed, streams_greedy_action (which masks by the observation's validity flags; ``mask=False`` is ``Agent.act(state, None)``:
+    the arg-max over all S rows, the invalid ones, whose embeddings are zero, included).  ``indices``: the forward's one index set
     (``points.draw_indices``); ``q_out`` as in streams_greedy_action; ``use_hip`` is handed to all three (``None``: each
     one's own default; ``True``: the whole forward in the defined float32 arithmetic, bit for bit what the CPU form gives);
     ``streams_form`` is streams_greedy_action's ``form``, ``embed_form`` embed's."""
     S = _embed_rows(state, embed_weights)
     sf = shape_features(state[:, 5 * S], points, indices, shape_weights, use_hip=use_hip)
     x, xg = embed(state, sf, embed_weights, use_hip=use_hip, form=embed_form)
-    return streams_greedy_action(x, xg, stream_weights, support, state.to(x.device), q_out=q_out, use_hip=use_hip, form=streams_form)
+    return streams_greedy_action(x, xg, stream_weights, support, state.to(x.device) if mask else None, q_out=q_out, use_hip=use_hip,
+                                 form=streams_form)
 
 
 # The same question for the order network's embedding stage (DESIGN.md section 3, "The order network"): torch's layers in the
