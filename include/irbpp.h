@@ -733,6 +733,33 @@ int irbpp_shape_features(const float* points_dev, int32_t n_shapes, int32_t n_po
 /* The number of chunks the k points are split into for this many shapes (small shape sets get more chunks, so that they
  * still fill the chip): what partial_dev must be sized by.  0 outside the limits above. */
 int irbpp_shape_features_chunks(int32_t n_shapes, int32_t k);
+/* replaces: the same shape branch in the forward that carries a gradient (Agent.learn's online forward: the gather of the
+ * sampled points, shapeEncoder per row with two [m_rows][k][hidden | feat] activation blocks kept for autograd, the max).
+ * irbpp_shape_features with a record: the same arguments, the same definition and the same bits in out_dev, and
+ *   arg_dev int32 [n_shapes][feat]: for a shape u that occurs in the ids the smallest j in [0, k) at which s_j[f] (before the
+ *   second leaky, compared as the max compares: -0 below +0, every NaN on top) is largest; -1 in every entry of a shape that
+ *   does not occur.
+ * Workspaces: partial_key_dev uint32 and partial_j_dev int32, each [n_shapes][partial_chunks][feat].  Two launches on
+ * `stream`, no atomics.  IRBPP_ERR_ARG as for irbpp_shape_features, and if arg_dev or a workspace is NULL. */
+int irbpp_shape_features_arg(const float* points_dev, int32_t n_shapes, int32_t n_points, const int32_t* indices_dev, int32_t k,
+                             const void* ids_dev, int32_t ids_are_float, int32_t ids_stride, int32_t m_rows,
+                             const irbpp_shape_encoder* enc, uint32_t* partial_key_dev, int32_t* partial_j_dev,
+                             int32_t partial_chunks, float* out_dev, int32_t out_stride, int32_t* arg_dev, void* stream);
+/* The backward of irbpp_shape_features_arg for the encoder's four arrays (the points and the ids carry no gradient), from
+ * grad_out_dev float32 [m_rows][feat], contiguous, and arg_dev as that call left it for the same points, indices, ids and
+ * encoder: d_w1_dev [hidden][3], d_b1_dev [hidden], d_w2_dev [feat][hidden], d_b2_dev [feat] are written, not added to.
+ * Defined float32 arithmetic (csrc/irbpp_shapefeat_grad.hip), reproducible bit for bit: the rows of grad_out are summed per
+ * shape in ascending m, each (shape, feature) passes its sum to the one point arg names, through the leaky's derivative at
+ * the recomputed s (s > 0 ? 1 : slope), and every sum over shapes or features is a chain in ascending order from +0.  Rows
+ * with an id outside [0, n_shapes) contribute nothing.  Two launches on `stream`, no atomics.
+ * Workspaces, both 16-byte aligned: point_d2_dev float32 [n_shapes][feat][4], first_dev float32 [n_shapes][hidden][4] (rows of
+ * shapes that do not occur are neither written nor used).
+ * IRBPP_ERR_ARG outside irbpp_shape_features' limits, for a NULL pointer or a misaligned workspace. */
+int irbpp_shape_features_backward(const float* points_dev, int32_t n_shapes, int32_t n_points, const int32_t* indices_dev, int32_t k,
+                                  const void* ids_dev, int32_t ids_are_float, int32_t ids_stride, int32_t m_rows,
+                                  const irbpp_shape_encoder* enc, const int32_t* arg_dev, const float* grad_out_dev,
+                                  float* point_d2_dev, float* first_dev, float* d_w1_dev, float* d_b1_dev, float* d_w2_dev,
+                                  float* d_b2_dev, void* stream);
 
 /* The layers of the embedding stage (model.py: heightEncoder = Conv2d(1, c1, 4, 2, 1) LeakyReLU Conv2d(c1, c2, 4, 2, 1) LeakyReLU
  * Conv2d(c2, c3, 3, 1, 1) LeakyReLU; init_candidate_embed = Linear(4, cand_hidden) LeakyReLU Linear(cand_hidden, cand_embed);

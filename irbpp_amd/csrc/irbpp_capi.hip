@@ -30,6 +30,7 @@
 #include "irbpp_streams.hip"        // the four noisy layers of the value and advantage streams in front of the dueling head (irbpp_noisy_weights, irbpp_streams_act)
 #include "irbpp_streams_mfma.hip"   // the same launch with the advantage stream on the matrix cores, the same bits (irbpp_streams_act_mfma)
 #include "irbpp_shapefeat.hip"      // the shape branch in front of the network: sampled points to shape features (irbpp_shape_features)
+#include "irbpp_shapefeat_grad.hip" // the same with a gradient: the arg record and the backward routed through it (irbpp_shape_features_arg, _backward)
 #include "irbpp_embed.hip"          // the embedding stage: heightmap CNN, candidate rows, masked mean (irbpp_embed)
 #include "irbpp_embed_mfma.hip"     // the same stage with the three per-row layers on the matrix cores, the same bits (irbpp_embed_mfma)
 #include "irbpp_order_embed.hip"   // the order network's embedding stage: CNN, k buffered items, one attention layer, mean (irbpp_order_embed)
@@ -1347,6 +1348,57 @@ int irbpp_shape_features(const float* points_dev, int32_t n_shapes, int32_t n_po
     const long long elems = (long long)m_rows * enc->feat;
     hipLaunchKernelGGL(irbpp_shape_gather_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const float*)partial_dev, ids_dev, out_dev, g);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+static bool shape_call_bad(const void* points_dev, int32_t n_shapes, int32_t n_points, const void* indices_dev, int32_t k,
+                           const void* ids_dev, int32_t ids_stride, int32_t m_rows, const irbpp_shape_encoder* enc) {
+    return !points_dev || !indices_dev || !ids_dev || !enc || !enc->w1 || !enc->b1 || !enc->w2 || !enc->b2 || enc->hidden < 1 ||
+           enc->hidden > SHAPE_MAX_WIDTH || enc->feat < 1 || enc->feat > SHAPE_MAX_WIDTH || !(enc->slope >= 0.0f) || k < 1 ||
+           k > SHAPE_MAX_POINTS || n_shapes < 1 || n_shapes > SHAPE_MAX_SHAPES || n_points < 1 || m_rows < 1 || ids_stride < 1;
+}
+
+int irbpp_shape_features_arg(const float* points_dev, int32_t n_shapes, int32_t n_points, const int32_t* indices_dev, int32_t k,
+                             const void* ids_dev, int32_t ids_are_float, int32_t ids_stride, int32_t m_rows,
+                             const irbpp_shape_encoder* enc, uint32_t* partial_key_dev, int32_t* partial_j_dev,
+                             int32_t partial_chunks, float* out_dev, int32_t out_stride, int32_t* arg_dev, void* stream) {
+    if (shape_call_bad(points_dev, n_shapes, n_points, indices_dev, k, ids_dev, ids_stride, m_rows, enc) || !partial_key_dev ||
+        !partial_j_dev || !out_dev || !arg_dev || out_stride < enc->feat || partial_chunks != shape_chunks(n_shapes, k))
+        return IRBPP_ERR_ARG;
+    ShapeArgs g;
+    g.ids_stride = ids_stride, g.m_rows = m_rows, g.out_stride = out_stride;
+    g.n_shapes = n_shapes, g.n_points = n_points, g.k = k, g.ids_are_float = ids_are_float != 0, g.hidden = enc->hidden;
+    g.feat = enc->feat, g.chunk_points = shape_chunk_points(n_shapes, k), g.chunks = partial_chunks, g.slope = enc->slope;
+    hipLaunchKernelGGL(irbpp_shape_partial_arg_kernel, dim3(n_shapes, partial_chunks), dim3(shape_threads(enc->feat)), 0,
+                       (hipStream_t)stream, points_dev, indices_dev, ids_dev, enc->w1, enc->b1, enc->w2, enc->b2, partial_key_dev,
+                       partial_j_dev, g);
+    if (hipGetLastError() != hipSuccess) return IRBPP_ERR_HIP;
+    const long long elems = ((long long)m_rows + n_shapes) * enc->feat;
+    hipLaunchKernelGGL(irbpp_shape_gather_arg_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const uint32_t*)partial_key_dev, (const int32_t*)partial_j_dev, ids_dev, out_dev, arg_dev, g);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+int irbpp_shape_features_backward(const float* points_dev, int32_t n_shapes, int32_t n_points, const int32_t* indices_dev, int32_t k,
+                                  const void* ids_dev, int32_t ids_are_float, int32_t ids_stride, int32_t m_rows,
+                                  const irbpp_shape_encoder* enc, const int32_t* arg_dev, const float* grad_out_dev,
+                                  float* point_d2_dev, float* first_dev, float* d_w1_dev, float* d_b1_dev, float* d_w2_dev,
+                                  float* d_b2_dev, void* stream) {
+    if (shape_call_bad(points_dev, n_shapes, n_points, indices_dev, k, ids_dev, ids_stride, m_rows, enc) || !arg_dev ||
+        !grad_out_dev || !point_d2_dev || !first_dev || (uintptr_t)point_d2_dev % 16 != 0 || (uintptr_t)first_dev % 16 != 0 ||
+        !d_w1_dev || !d_b1_dev || !d_w2_dev || !d_b2_dev)
+        return IRBPP_ERR_ARG;
+    ShapeGradArgs g;
+    g.ids_stride = ids_stride, g.m_rows = m_rows, g.n_shapes = n_shapes, g.n_points = n_points, g.k = k;
+    g.ids_are_float = ids_are_float != 0, g.hidden = enc->hidden, g.feat = enc->feat, g.slope = enc->slope;
+    hipLaunchKernelGGL(irbpp_shape_backward_shape_kernel, dim3(n_shapes), dim3(SHAPE_GRAD_THREADS), 0, (hipStream_t)stream, points_dev,
+                       indices_dev, ids_dev, enc->w1, enc->b1, enc->w2, enc->b2, arg_dev, grad_out_dev, (ShapeQuad*)point_d2_dev,
+                       (ShapeQuad*)first_dev, g);
+    if (hipGetLastError() != hipSuccess) return IRBPP_ERR_HIP;
+    const long long elems = (long long)enc->feat * enc->hidden + enc->feat + 4LL * enc->hidden;
+    hipLaunchKernelGGL(irbpp_shape_backward_reduce_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       enc->w1, enc->b1, arg_dev, (const ShapeQuad*)point_d2_dev, (const ShapeQuad*)first_dev, d_w1_dev, d_b1_dev,
+                       d_w2_dev, d_b2_dev, g);
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
 }
 

@@ -1092,6 +1092,20 @@ class ShapePoints(object):
             self._workspace[key] = torch.empty((self.n_shapes, chunks, feat), dtype=torch.float32, device=self.device)
         return self._workspace[key]
 
+    def _partial_arg(self, chunks: int, feat: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """irbpp_shape_features_arg's two workspaces: the chunks' keys and positions, int32 [n_shapes, chunks, feat] each."""
+        key = ("arg", chunks, feat)
+        if key not in self._workspace:
+            self._workspace[key] = tuple(torch.empty((self.n_shapes, chunks, feat), dtype=torch.int32, device=self.device) for _ in range(2))
+        return self._workspace[key]
+
+    def _grad_workspace(self, hidden: int, feat: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """irbpp_shape_features_backward's two workspaces: float32 [n_shapes, feat, 4] and [n_shapes, hidden, 4]."""
+        key = ("grad", hidden, feat)
+        if key not in self._workspace:
+            self._workspace[key] = tuple(torch.empty((self.n_shapes, n, 4), dtype=torch.float32, device=self.device) for n in (feat, hidden))
+        return self._workspace[key]
+
 
 class ShapeEncoderWeights(object):
     """``shapeEncoder``'s two Linear layers as float32 contiguous tensors (w1 [H1, 3], b1 [H1], w2 [F, H1], b2 [F]) and the
@@ -1228,6 +1242,198 @@ def shape_features(ids: torch.Tensor, points: ShapePoints, indices: torch.Tensor
                                         _p(points._partial(chunks, F_)), chunks, _p(out), max(int(out.stride(0)), F_),
                                         _stream(dev)), "irbpp_shape_features")
     return out
+
+
+# The shape branch in the forward that carries a gradient ("The shape branch with a gradient"): the
+# parent's path (ShapePoints.gather into torch's layers, per row), torch's layers on the unique ids, or the four launches of
+# irbpp_shape_features_arg / irbpp_shape_features_backward.  The kernels: tools/shape_grad_rates.py measured forward plus
+# backward on an MI355X at 0.27 ms against 1.01 ms for torch on the unique ids and 4.14 ms for the parent's path at 640 rows of
+# the 64 BlockOut shapes, 0.43 against 1.80 and 4.15 ms with 200 shapes, and 0.27 / 0.22 against 0.79 / 0.77 and 0.68 / 0.67 ms
+# at 64 rows: beyond the larger spread at every measured size (profiles/shape_grad/).  use_hip=False asks for torch's layers.
+SHAPE_GRAD_HIP_DEFAULT = True
+
+
+def _shape_points_np(table, s: int, idx):
+    """table[s][idx] as float32 [len(idx), 3], a NaN point for every index outside the table."""
+    import numpy as np
+    bad = (idx < 0) | (idx >= table.shape[1])
+    p = table[s][np.where(bad, 0, idx)].astype(np.float32)
+    p[bad] = np.nan
+    return p
+
+
+def _shape_key_np(h):
+    import numpy as np
+    b = np.ascontiguousarray(h, dtype=np.float32).view(np.uint32)
+    key = np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000))
+    return np.where((b & np.uint32(0x7fffffff)) > np.uint32(0x7f800000), np.uint32(0xffffffff), key)
+
+
+def _shape_grad_forward_np(table, idx, u, w1, b1, w2, b2, slope: float):
+    """The definition of csrc/irbpp_shapefeat_grad.hip's forward on numpy arrays: table float32 [n_shapes, P, 3], idx int64
+    [k], u int64 [M] with -1 for a bad id -> (out float32 [M, F], the bits of _shape_features_cpu; arg int32 [n_shapes, F])."""
+    import numpy as np
+    f32 = np.float32
+    leaky = lambda s: np.where(s > 0, s, f32(slope) * s).astype(f32)  # noqa: E731
+    out = np.full((u.shape[0], w2.shape[0]), np.nan, dtype=f32)
+    arg = np.full((table.shape[0], w2.shape[0]), -1, dtype=np.int32)
+    with np.errstate(all="ignore"):
+        for s in np.unique(u[u >= 0]):
+            s2 = _lin_np(w2, b2, leaky(_lin_np(w1, b1, _shape_points_np(table, s, idx))))
+            out[u == s] = _max_sticky_np(leaky(s2))
+            arg[s] = np.argmax(_shape_key_np(s2), axis=0)          # the first position of the largest key
+    return out, arg
+
+
+def _shape_grad_backward_np(table, idx, u, w1, b1, w2, b2, slope: float, arg, g):
+    """The definition's backward: g float32 [M, F] -> (dW1 [H1, 3], db1 [H1], dW2 [F, H1], db2 [F]), every chain in its order."""
+    import numpy as np
+    f32 = np.float32
+    sl = f32(slope)
+    H1, F_ = w1.shape[0], w2.shape[0]
+    G = np.zeros((table.shape[0], F_), dtype=f32)
+    d_w1, d_b1, d_w2, d_b2 = np.zeros((H1, 3), f32), np.zeros(H1, f32), np.zeros((F_, H1), f32), np.zeros(F_, f32)
+    with np.errstate(all="ignore"):
+        for m in range(u.shape[0]):                          # m ascending; a bad id's row adds nothing
+            if u[m] >= 0:
+                G[u[m]] = G[u[m]] + g[m]
+        for s in np.unique(u[u >= 0]):                       # u ascending
+            j = arg[s].astype(np.int64)
+            p = _shape_points_np(table, s, np.where((j >= 0) & (j < idx.shape[0]), idx[np.clip(j, 0, idx.shape[0] - 1)], -1))   # [F, 3]
+            s1 = _lin_np(w1, b1, p)                          # [F, H1]
+            h1 = np.where(s1 > 0, s1, sl * s1).astype(f32)
+            s2 = b2.astype(f32)
+            for i in range(H1):
+                s2 = _fmaf_np(h1[:, i], w2[:, i], s2)
+            d2 = np.where(s2 > 0, G[s], sl * G[s]).astype(f32)
+            d_b2 = d_b2 + d2
+            d_w2 = _fmaf_np(d2[:, None], h1, d_w2)
+            e = d2[:, None] * w2
+            ds1 = np.where(s1 > 0, e, sl * e).astype(f32)
+            first, first_b = np.zeros((H1, 3), f32), np.zeros(H1, f32)
+            for f in range(F_):                              # f ascending
+                first = _fmaf_np(ds1[f][:, None], p[f][None, :], first)
+                first_b = first_b + ds1[f]
+            d_w1, d_b1 = d_w1 + first, d_b1 + first_b
+    return d_w1, d_b1, d_w2, d_b2
+
+
+class _ShapeFeaturesGrad(torch.autograd.Function):
+    """shape_features with the arg record kept for a backward that reaches the encoder's four arrays: the numpy definition on
+    CPU tensors, irbpp_shape_features_arg / irbpp_shape_features_backward on a HIP device."""
+
+    @staticmethod
+    def forward(ctx, w1, b1, w2, b2, ids, indices, points, slope, lib):
+        dev = points.device
+        M, k, H1, F_ = int(ids.shape[0]), int(indices.shape[0]), int(w1.shape[0]), int(w2.shape[0])
+        ctx.points, ctx.slope, ctx.lib = points, slope, lib
+        if lib is None:
+            import numpy as np
+            n = lambda t: t.detach().cpu().numpy()           # noqa: E731
+            out, arg = _shape_grad_forward_np(n(points.points), n(indices).astype(np.int64), _shape_ids(ids, points.n_shapes).numpy(),
+                                              n(w1), n(b1), n(w2), n(b2), slope)
+            out, arg = torch.from_numpy(out), torch.from_numpy(arg)
+        else:
+            from . import _lib
+            out = torch.empty((M, F_), dtype=torch.float32, device=dev)
+            arg = torch.empty((points.n_shapes, F_), dtype=torch.int32, device=dev)
+            chunks = lib.irbpp_shape_features_chunks(points.n_shapes, k)
+            key_ws, j_ws = points._partial_arg(chunks, F_)
+            enc = _IrbppShapeEncoder(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), H1, F_, slope)
+            _lib.check(lib.irbpp_shape_features_arg(_p(points.points), points.n_shapes, points.n_points, _p(indices), k, _p(ids),
+                                                    1 if ids.is_floating_point() else 0, max(int(ids.stride(0)), 1), M, C.byref(enc),
+                                                    _p(key_ws), _p(j_ws), chunks, _p(out), F_, _p(arg), _stream(dev)),
+                       "irbpp_shape_features_arg")
+        ctx.save_for_backward(w1, b1, w2, b2, ids, indices, arg)
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_arg):
+        w1, b1, w2, b2, ids, indices, arg = ctx.saved_tensors
+        points, slope, lib = ctx.points, ctx.slope, ctx.lib
+        g = grad_out.detach().to(torch.float32).contiguous()
+        if lib is None:
+            import numpy as np
+            n = lambda t: t.detach().cpu().numpy()           # noqa: E731
+            grads = _shape_grad_backward_np(n(points.points), n(indices).astype(np.int64), _shape_ids(ids, points.n_shapes).numpy(),
+                                            n(w1), n(b1), n(w2), n(b2), slope, n(arg), n(g))
+            grads = tuple(torch.from_numpy(np.ascontiguousarray(t)) for t in grads)
+        else:
+            from . import _lib
+            dev = points.device
+            H1, F_ = int(w1.shape[0]), int(w2.shape[0])
+            grads = tuple(torch.empty_like(t) for t in (w1, b1, w2, b2))
+            pd_ws, first_ws = points._grad_workspace(H1, F_)
+            enc = _IrbppShapeEncoder(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), H1, F_, slope)
+            _lib.check(lib.irbpp_shape_features_backward(_p(points.points), points.n_shapes, points.n_points, _p(indices),
+                                                         int(indices.shape[0]), _p(ids), 1 if ids.is_floating_point() else 0,
+                                                         max(int(ids.stride(0)), 1), int(ids.shape[0]), C.byref(enc), _p(arg), _p(g),
+                                                         _p(pd_ws), _p(first_ws), *(_p(t) for t in grads), _stream(dev)),
+                       "irbpp_shape_features_backward")
+        return grads + (None,) * 5
+
+
+def _shape_features_grad_torch(ids, points: ShapePoints, indices, w1, b1, w2, b2, slope: float) -> torch.Tensor:
+    """torch's layers on the unique ids, with autograd (the bad ids' rows and a bad index as in _shape_features_torch)."""
+    F = torch.nn.functional
+    u = _shape_ids(ids, points.n_shapes)
+    idx = indices.long()
+    bad_idx = ((idx < 0) | (idx >= points.n_points)).any()
+    uniq, inv = torch.unique(u.clamp(min=0), return_inverse=True)
+    p = points.points[uniq[:, None], idx.clamp(0, points.n_points - 1)[None, :]]
+    h = F.leaky_relu(F.linear(F.leaky_relu(F.linear(p, w1, b1), slope), w2, b2), slope)
+    feat = torch.max(h, dim=1)[0][inv]
+    return torch.where((u < 0)[:, None] | bad_idx, torch.full_like(feat, float("nan")), feat)
+
+
+def shape_features_grad(ids: torch.Tensor, points: ShapePoints, indices: torch.Tensor, linear1, linear2,
+                        negative_slope: float = 0.01, *, use_hip: Optional[bool] = None, return_arg: bool = False):
+    """The shape branch of the forward that carries a gradient (Agent.learn's online forward, model.py:328-335, :365-372):
+    ``shape_features`` over the live parameters of ``shapeEncoder``'s two Linear layers -> ``shape_feature`` float32 [M, F]
+    with a ``grad_fn``, in place of ``torch.max(shapeEncoder(points.gather(ids, indices)), dim=1)[0]``.  ``ids`` and
+    ``indices`` as shape_features takes them.  The feature is computed once per distinct id and the max routes each feature's
+    gradient to one point, so the backward costs (distinct ids) x F x H1 fused multiply-adds and keeps no activation block.
+
+    Forms: on CPU tensors the numpy emulation of the definition (csrc/irbpp_shapefeat_grad.hip), forward and backward; on a
+    HIP device with ``use_hip=True`` (``None`` takes SHAPE_GRAD_HIP_DEFAULT) irbpp_shape_features_arg and, in the backward,
+    irbpp_shape_features_backward: the forward's bits are shape_features', the four gradients are reproducible bit for bit
+    (ordered chains, no atomics) and equal to the CPU form's; else torch's layers on the unique ids with torch's autograd.
+    The points and the ids carry no gradient.  ``return_arg=True`` returns ``(shape_feature, arg)``, arg int32 [n_shapes, F]:
+    the position in ``indices`` of each feature's maximum per shape that occurs (the smallest one among ties), -1 elsewhere;
+    the torch form keeps no such record and raises."""
+    dev = points.device
+    slope = float(negative_slope)
+    w1, b1, w2, b2 = linear1.weight, linear1.bias, linear2.weight, linear2.bias
+    H1, F_ = int(w1.shape[0]), int(w2.shape[0])
+    if tuple(w1.shape) != (H1, 3) or tuple(w2.shape) != (F_, H1) or tuple(b1.shape) != (H1,) or tuple(b2.shape) != (F_,):
+        raise ValueError("shape encoder: Linear(3, H1) and Linear(H1, F) with biases")
+    if not (1 <= H1 <= SHAPE_MAX_WIDTH and 1 <= F_ <= SHAPE_MAX_WIDTH and slope >= 0):
+        raise ValueError("shape encoder: 1 <= H1, F <= 256 and negative_slope >= 0")
+    if any(t.device != dev for t in (w1, b1, w2, b2)):
+        raise ValueError("shape_features_grad: the layers and the points live on different devices")
+    ids = ids.detach()
+    if ids.device != dev:
+        ids = ids.to(dev)
+    if ids.is_floating_point():
+        ids = ids if ids.dtype == torch.float32 else ids.to(torch.float32)
+    elif ids.dtype != torch.int64:
+        ids = ids.long()
+    ids = ids.reshape(-1)
+    indices = indices.detach().to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    M, k = int(ids.shape[0]), int(indices.shape[0])
+    if not (1 <= k <= SHAPE_MAX_POINTS) or M < 1 or points.n_shapes > SHAPE_MAX_SHAPES:
+        raise ValueError("shape_features_grad: indices int [k] with 1 <= k <= 4096, at least one id, at most 65535 shapes")
+    lib = _head_lib(points.points, use_hip, SHAPE_GRAD_HIP_DEFAULT)
+    if lib is None and dev.type == "cuda":
+        if return_arg:
+            raise ValueError("shape_features_grad: torch's layers keep no arg record")
+        return _shape_features_grad_torch(ids, points, indices, w1, b1, w2, b2, slope)
+    if lib is not None and M > 1 and ids.stride(0) < 1:
+        ids = ids.contiguous()
+    live = tuple(t.to(torch.float32).contiguous() for t in (w1, b1, w2, b2))     # the parameters themselves where they are both
+    out, arg = _ShapeFeaturesGrad.apply(*live, ids, indices, points, slope, lib)
+    return (out, arg) if return_arg else out
 
 
 # The same question for the embedding stage between the two (DESIGN.md section 3, "The embedding stage"): torch's layers in
