@@ -702,6 +702,42 @@ int irbpp_streams_act_mfma(const irbpp_stream_weights* w, const float* xg_dev, i
                            int32_t obs_stride, int32_t s_rows, int32_t n_env, int64_t* action_dev /* may be NULL */,
                            float* q_out_dev, int64_t q_stride, float* v_out_dev, float* a_out_dev, void* stream);
 
+/* The noise of the four layers (NoisyLinear's weight_epsilon [out][in] and bias_epsilon [out] buffers), float32 on the device
+ * and contiguous, named as in irbpp_stream_weights. */
+typedef struct { const float *w_hv, *b_hv, *w_zv, *b_zv, *w_ha, *b_ha, *w_za, *b_za; } irbpp_stream_noise;
+/* Where irbpp_streams_backward writes the gradients of the four layers' sixteen parameter tensors (hv = fc_h_v, zv = fc_z_v,
+ * ha = fc_h_a, za = fc_z_a), float32 on the device, contiguous, each of its parameter's shape.  Any of them may be NULL: that
+ * parameter needs no gradient. */
+typedef struct { float *hv_weight_mu, *hv_weight_sigma, *hv_bias_mu, *hv_bias_sigma, *zv_weight_mu, *zv_weight_sigma, *zv_bias_mu,
+                 *zv_bias_sigma, *ha_weight_mu, *ha_weight_sigma, *ha_bias_mu, *ha_bias_sigma, *za_weight_mu, *za_weight_sigma,
+                 *za_bias_mu, *za_bias_sigma; } irbpp_stream_grads;
+/* replaces: autograd's way back through the four noisy layers of the streams (model.py:393-394, NoisyLinear.forward :224-228)
+ * in Agent.learn's online forward, from the gradients of the logits irbpp_streams_act wrote to v_out_dev and a_out_dev:
+ * gv_dev float32 [batch][atoms] and ga_dev float32 [batch][s_rows][atoms], contiguous.  Either may be NULL: it counts as
+ * zeros, nothing is launched for its stream and that stream's outputs are +0.  w, xg_dev, x_dev and their strides as given to
+ * irbpp_streams_act (w the effective weights); eps the layers' noise, NULL in eval mode (the sigma outputs are then left
+ * alone).  Outputs, written and not added to, each may be NULL: dx_dev float32 [batch][s_rows][embed] and dxg_dev float32
+ * [batch][embed], contiguous, and the sixteen tensors of grads: weight_mu = dW, weight_sigma = dW * weight_epsilon,
+ * bias_mu = db, bias_sigma = db * bias_epsilon.  Defined float32 arithmetic (csrc/irbpp_streams_grad.hip), reproducible bit
+ * for bit: the pre-activations are the forward's chains again; per row e[j] is the chain over the atoms of g[t] W_z[t][j] from
+ * +0, d[j] = e[j] where the pre-activation is > 0 and +0 elsewhere, dx[k] the chain over j of d[j] W_h[j][k]; the advantage
+ * stream's weight gradients are per sample chains over the rows, summed over the samples in ascending order with plain adds,
+ * the value stream's chains over the samples; single-rounding fused multiply-adds, never split or re-associated, no atomics.
+ * The bits depend on the data and (batch, s_rows) alone.  workspace_dev: irbpp_streams_backward_workspace bytes, written
+ * before it is read.  At most four launches on `stream`.  Finite inputs are the contract: a NaN or an infinity gives
+ * unspecified values and touches nothing out of range.
+ * IRBPP_ERR_ARG unless 1 <= embed, hidden <= 256, 2 <= atoms <= 128, 1 <= s_rows <= 1024, 1 <= batch <= 1024, the strides as
+ * for irbpp_streams_act, and w, its eight arrays, grads, xg_dev, x_dev, workspace_dev and, where eps is given, its eight
+ * arrays are not NULL. */
+int irbpp_streams_backward(const irbpp_stream_weights* w, const irbpp_stream_noise* eps /* NULL: eval mode */, const float* xg_dev,
+                           int64_t xg_stride, const float* x_dev, int64_t env_stride, int64_t row_stride,
+                           const float* ga_dev /* may be NULL */, const float* gv_dev /* may be NULL */, int32_t s_rows,
+                           int32_t batch, float* workspace_dev, float* dx_dev, float* dxg_dev, const irbpp_stream_grads* grads,
+                           void* stream);
+/* The bytes of irbpp_streams_backward's workspace: batch * (hidden*embed + atoms*hidden + hidden + atoms + 2*hidden) floats --
+ * per sample the advantage stream's four partials and the value stream's hidden row and its gradient.  0 outside the limits. */
+int64_t irbpp_streams_backward_workspace(int32_t embed, int32_t hidden, int32_t atoms, int32_t s_rows, int32_t batch);
+
 /* The shape encoder (model.py: shapeEncoder = Linear(3, hidden) LeakyReLU Linear(hidden, feat) LeakyReLU), float32 on the
  * device, row-major and contiguous: w1 [hidden][3], b1 [hidden], w2 [feat][hidden], b2 [feat]; slope is the LeakyReLU's
  * negative_slope (0.01 in the reference), >= 0. */

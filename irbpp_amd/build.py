@@ -9,7 +9,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libirbpp_hip.so")
 SOURCES = ["irbpp_capi.hip", "irbpp_kernels.hip", "irbpp_wide.hip", "irbpp_replay.hip", "irbpp_replay_pool.hip", "irbpp_metrics.hip", "irbpp_metrics.h", "irbpp_device.h", "contours_device.h", "irbpp_itemgen.h",
-           "irbpp_itemgen.hip", "irbpp_itemgen_device.h", "irbpp_rotalias.h", "irbpp_head.h", "irbpp_c51.hip", "irbpp_dueling.hip", "irbpp_dueling_loss.hip", "irbpp_optim.hip", "irbpp_streams.hip", "irbpp_streams_mfma.hip", "irbpp_mfma_chain.h", "irbpp_front.h", "irbpp_shapefeat.hip", "irbpp_shapefeat_grad.hip", "irbpp_embed.hip", "irbpp_embed_mfma.hip", "irbpp_order_embed.hip", "irbpp_order_embed_mfma.hip", "irbpp_plan.h", "irbpp_binstate.h", "irbpp_binstate.hip", "irbpp_rounds.h",
+           "irbpp_itemgen.hip", "irbpp_itemgen_device.h", "irbpp_rotalias.h", "irbpp_head.h", "irbpp_c51.hip", "irbpp_dueling.hip", "irbpp_dueling_loss.hip", "irbpp_optim.hip", "irbpp_streams.hip", "irbpp_streams_mfma.hip", "irbpp_streams_grad.hip", "irbpp_mfma_chain.h", "irbpp_front.h", "irbpp_shapefeat.hip", "irbpp_shapefeat_grad.hip", "irbpp_embed.hip", "irbpp_embed_mfma.hip", "irbpp_order_embed.hip", "irbpp_order_embed_mfma.hip", "irbpp_plan.h", "irbpp_binstate.h", "irbpp_binstate.hip", "irbpp_rounds.h",
            os.path.join("..", "..", "include", "irbpp.h")]
 # -ffp-contract=off: the float64 results must equal numpy's, so no FMA contraction anywhere
 # -fno-honor-nans: no NaN ever enters the path, so fmax needs no canonicalising v_max(x,x) per use

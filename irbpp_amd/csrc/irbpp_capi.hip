@@ -31,6 +31,7 @@
 #include "irbpp_streams_mfma.hip"   // the same launch with the advantage stream on the matrix cores, the same bits (irbpp_streams_act_mfma)
 #include "irbpp_shapefeat.hip"      // the shape branch in front of the network: sampled points to shape features (irbpp_shape_features)
 #include "irbpp_shapefeat_grad.hip" // the same with a gradient: the arg record and the backward routed through it (irbpp_shape_features_arg, _backward)
+#include "irbpp_streams_grad.hip"   // the backward of the streams' four noisy layers: dx, dxg and the sixteen parameter gradients (irbpp_streams_backward)
 #include "irbpp_embed.hip"          // the embedding stage: heightmap CNN, candidate rows, masked mean (irbpp_embed)
 #include "irbpp_embed_mfma.hip"     // the same stage with the three per-row layers on the matrix cores, the same bits (irbpp_embed_mfma)
 #include "irbpp_order_embed.hip"   // the order network's embedding stage: CNN, k buffered items, one attention layer, mean (irbpp_order_embed)
@@ -1320,6 +1321,66 @@ int irbpp_streams_act_mfma(const irbpp_stream_weights* w, const float* xg_dev, i
     if (!dueling_lds((const void*)irbpp_streams_finish_kernel, w->atoms, s_rows, &lds)) return IRBPP_ERR_HIP;
     hipLaunchKernelGGL(irbpp_streams_finish_kernel, dim3(n_env), dim3(DUELING_THREADS), lds, (hipStream_t)stream, w->w_hv, w->b_hv,
                        w->w_zv, w->b_zv, xg_dev, (const float*)a_out_dev, support_dev, obs_dev, action_dev, q_out_dev, g);
+    return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
+}
+
+static bool streams_grad_shape_bad(int32_t embed, int32_t hidden, int32_t atoms, int32_t s_rows, int32_t batch) {
+    return embed < 1 || embed > STREAMS_GRAD_MAX_WIDTH || hidden < 1 || hidden > STREAMS_GRAD_MAX_WIDTH || atoms < 2 ||
+           atoms > HEAD_MAX_ATOMS || s_rows < 1 || s_rows > HEAD_MAX_ROWS || batch < 1 || batch > STREAMS_GRAD_MAX_BATCH;
+}
+
+int64_t irbpp_streams_backward_workspace(int32_t embed, int32_t hidden, int32_t atoms, int32_t s_rows, int32_t batch) {
+    if (streams_grad_shape_bad(embed, hidden, atoms, s_rows, batch)) return 0;
+    return (int64_t)batch * streams_grad_sample_floats(embed, hidden, atoms) * (int64_t)sizeof(float);
+}
+
+int irbpp_streams_backward(const irbpp_stream_weights* w, const irbpp_stream_noise* eps, const float* xg_dev, int64_t xg_stride,
+                           const float* x_dev, int64_t env_stride, int64_t row_stride, const float* ga_dev, const float* gv_dev,
+                           int32_t s_rows, int32_t batch, float* workspace_dev, float* dx_dev, float* dxg_dev,
+                           const irbpp_stream_grads* grads, void* stream) {
+    if (!w || !grads || !w->w_hv || !w->b_hv || !w->w_zv || !w->b_zv || !w->w_ha || !w->b_ha || !w->w_za || !w->b_za ||
+        streams_grad_shape_bad(w->embed, w->hidden, w->atoms, s_rows, batch) || !workspace_dev || !xg_dev ||
+        xg_stride < w->embed || !x_dev || row_stride < w->embed || env_stride < (int64_t)(s_rows - 1) * row_stride + w->embed ||
+        (eps && (!eps->w_hv || !eps->b_hv || !eps->w_zv || !eps->b_zv || !eps->w_ha || !eps->b_ha || !eps->w_za || !eps->b_za)))
+        return IRBPP_ERR_ARG;
+    const hipStream_t st = (hipStream_t)stream;
+    StreamsGradArgs g;
+    g.xg_stride = xg_stride, g.env_stride = env_stride, g.row_stride = row_stride;
+    g.embed = w->embed, g.hidden = w->hidden, g.atoms = w->atoms, g.s_rows = s_rows, g.batch = batch;
+    g.w_ha_vec4 = (w->embed % 4 == 0 && (uintptr_t)w->w_ha % 16 == 0) ? 1 : 0;
+    g.w_za_vec4 = (w->hidden % 4 == 0 && (uintptr_t)w->w_za % 16 == 0) ? 1 : 0;
+    if (gv_dev) {
+        hipLaunchKernelGGL(irbpp_streams_grad_value_kernel, dim3(batch), dim3(STREAMS_GRAD_VALUE_THREADS), 0, st, w->w_hv, w->b_hv,
+                           w->w_zv, xg_dev, gv_dev, workspace_dev, dxg_dev, g);
+    } else if (dxg_dev) {
+        const long long n = (long long)batch * w->embed;
+        hipLaunchKernelGGL(irbpp_streams_grad_zero_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dxg_dev, n);
+    }
+    if (hipGetLastError() != hipSuccess) return IRBPP_ERR_HIP;
+    if (ga_dev) {
+        const size_t lds = streams_grad_lds_bytes(w->embed, w->hidden, w->atoms);
+        if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)irbpp_streams_grad_rows_kernel,
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return IRBPP_ERR_HIP;
+        hipLaunchKernelGGL(irbpp_streams_grad_rows_kernel, dim3(batch), dim3(STREAMS_GRAD_THREADS), lds, st, w->w_ha, w->b_ha, w->w_za,
+                           x_dev, ga_dev, workspace_dev, dx_dev, g);
+    } else if (dx_dev) {
+        const long long n = (long long)batch * s_rows * w->embed;
+        hipLaunchKernelGGL(irbpp_streams_grad_zero_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dx_dev, n);
+    }
+    if (hipGetLastError() != hipSuccess) return IRBPP_ERR_HIP;
+    StreamsGradOut oa, ov;
+    oa.h_w_mu = grads->ha_weight_mu, oa.h_w_sigma = grads->ha_weight_sigma, oa.h_b_mu = grads->ha_bias_mu, oa.h_b_sigma = grads->ha_bias_sigma;
+    oa.z_w_mu = grads->za_weight_mu, oa.z_w_sigma = grads->za_weight_sigma, oa.z_b_mu = grads->za_bias_mu, oa.z_b_sigma = grads->za_bias_sigma;
+    ov.h_w_mu = grads->hv_weight_mu, ov.h_w_sigma = grads->hv_weight_sigma, ov.h_b_mu = grads->hv_bias_mu, ov.h_b_sigma = grads->hv_bias_sigma;
+    ov.z_w_mu = grads->zv_weight_mu, ov.z_w_sigma = grads->zv_weight_sigma, ov.z_b_mu = grads->zv_bias_mu, ov.z_b_sigma = grads->zv_bias_sigma;
+    oa.h_w_eps = eps ? eps->w_ha : nullptr, oa.h_b_eps = eps ? eps->b_ha : nullptr, oa.z_w_eps = eps ? eps->w_za : nullptr;
+    oa.z_b_eps = eps ? eps->b_za : nullptr;
+    ov.h_w_eps = eps ? eps->w_hv : nullptr, ov.h_b_eps = eps ? eps->b_hv : nullptr, ov.z_w_eps = eps ? eps->w_zv : nullptr;
+    ov.z_b_eps = eps ? eps->b_zv : nullptr;
+    const long long elems = 2 * ((long long)w->hidden * w->embed + (long long)w->atoms * w->hidden + w->hidden + w->atoms);
+    hipLaunchKernelGGL(irbpp_streams_grad_reduce_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st,
+                       (const float*)workspace_dev, xg_dev, gv_dev, oa, ov, ga_dev ? 1 : 0, gv_dev ? 1 : 0, g);
     return hipGetLastError() == hipSuccess ? IRBPP_OK : IRBPP_ERR_HIP;
 }
 

@@ -1046,6 +1046,190 @@ def streams_logits(x: torch.Tensor, x_global: torch.Tensor, weights: StreamWeigh
     return _streams_logits_cpu(x, xg, weights)
 
 
+# The streams in the forward that carries a gradient ("The noisy streams with a gradient"): torch's four
+# layers under autograd or the forward's kernel and the launches of irbpp_streams_backward.  Torch's layers, since
+# tools/streams_grad_rates.py measured forward plus backward on an MI355X at 0.99 ms against 1.63 ms for the kernels (1.46 ms
+# with form="mfma") at B = 64, S = 500, widths 128, 31 atoms, and 2.49 against 3.05 (2.57) ms at B = 512
+# (profiles/streams_grad/): the kernels are ahead at neither size; what they buy is a backward that gives the same bits on
+# every run.  use_hip=True asks for the kernels.
+STREAMS_GRAD_HIP_DEFAULT = False
+
+STREAMS_GRAD_MAX_BATCH = 1024
+_NOISY_PARAMS = ("weight_mu", "weight_sigma", "bias_mu", "bias_sigma")
+
+
+class _IrbppStreamNoise(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("w_hv", "b_hv", "w_zv", "b_zv", "w_ha", "b_ha", "w_za", "b_za")]
+
+
+class _IrbppStreamGrads(C.Structure):
+    _fields_ = [(f"{layer}_{p}", C.c_void_p) for layer in ("hv", "zv", "ha", "za") for p in _NOISY_PARAMS]
+
+
+def _streams_grad_stream_np(x, w_h, b_h, w_z, g):
+    """One stream of the definition's backward on float32 numpy arrays, per row: x [..., E], g [..., A] ->
+    (h = relu(pre-activation) [..., H], d [..., H], dx [..., E]), every chain ascending from its start."""
+    import numpy as np
+    f32 = np.float32
+    p = _lin_np(w_h, b_h, x)
+    on = p > 0
+    e = np.zeros(p.shape, f32)
+    for t in range(w_z.shape[0]):
+        e = _fmaf_np(g[..., t:t + 1], w_z[t], e)
+    d = np.where(on, e, f32(0)).astype(f32)
+    dx = np.zeros(x.shape, f32)
+    for j in range(w_h.shape[0]):
+        dx = _fmaf_np(d[..., j:j + 1], w_h[j], dx)
+    return np.where(on, p, f32(0)).astype(f32), d, dx
+
+
+def _streams_grad_backward_np(x, xg, w, eps, ga, gv):
+    """The definition of csrc/irbpp_streams_grad.hip on float32 numpy arrays: x [B, S, E], xg [B, E], w the eight effective
+    arrays in StreamWeights' order (w_hv, b_hv, w_zv, b_zv, w_ha, b_ha, w_za, b_za), eps the eight epsilon arrays in the same
+    order or None (eval mode), ga [B, S, A] or None, gv [B, A] or None -> (dx, dxg, grads): grads maps "hv_weight_mu" ...
+    "za_bias_sigma" to arrays (the sigmas to None in eval mode).  A missing gradient counts as zeros."""
+    import numpy as np
+    f32 = np.float32
+    w_hv, b_hv, w_zv, b_zv, w_ha, b_ha, w_za, b_za = w
+    B, S, E = x.shape
+    H, A = w_ha.shape[0], w_za.shape[0]
+    d_w = {n: np.zeros(s, f32) for n, s in (("hv_w", (H, E)), ("hv_b", (H,)), ("zv_w", (A, H)), ("zv_b", (A,)), ("ha_w", (H, E)),
+                                            ("ha_b", (H,)), ("za_w", (A, H)), ("za_b", (A,)))}
+    dx, dxg = np.zeros((B, S, E), f32), np.zeros((B, E), f32)
+    with np.errstate(all="ignore"):
+        if ga is not None:
+            ha, d, dx = _streams_grad_stream_np(x, w_ha, b_ha, w_za, ga)
+            p_za, p_ha = np.zeros((B, A, H), f32), np.zeros((B, H, E), f32)
+            pb_za, pb_ha = np.zeros((B, A), f32), np.zeros((B, H), f32)
+            for s in range(S):                               # per sample, s ascending
+                p_za = _fmaf_np(ga[:, s, :, None], ha[:, s, None, :], p_za)
+                p_ha = _fmaf_np(d[:, s, :, None], x[:, s, None, :], p_ha)
+                pb_za, pb_ha = pb_za + ga[:, s], pb_ha + d[:, s]
+            for b in range(B):                               # plain adds, b ascending
+                d_w["za_w"], d_w["ha_w"] = d_w["za_w"] + p_za[b], d_w["ha_w"] + p_ha[b]
+                d_w["za_b"], d_w["ha_b"] = d_w["za_b"] + pb_za[b], d_w["ha_b"] + pb_ha[b]
+        if gv is not None:
+            hv, dv, dxg = _streams_grad_stream_np(xg, w_hv, b_hv, w_zv, gv)
+            for b in range(B):                               # one chain over b
+                d_w["zv_w"] = _fmaf_np(gv[b][:, None], hv[b][None, :], d_w["zv_w"])
+                d_w["hv_w"] = _fmaf_np(dv[b][:, None], xg[b][None, :], d_w["hv_w"])
+                d_w["zv_b"], d_w["hv_b"] = d_w["zv_b"] + gv[b], d_w["hv_b"] + dv[b]
+        grads = {}
+        for i, layer in enumerate(("hv", "zv", "ha", "za")):
+            dw, db = d_w[layer + "_w"], d_w[layer + "_b"]
+            grads[layer + "_weight_mu"], grads[layer + "_bias_mu"] = dw, db
+            grads[layer + "_weight_sigma"] = None if eps is None else (dw * eps[2 * i]).astype(f32)
+            grads[layer + "_bias_sigma"] = None if eps is None else (db * eps[2 * i + 1]).astype(f32)
+    return dx, dxg, grads
+
+
+def _streams_grad_workspace(lib, w: StreamWeights, S: int, B: int, dev) -> torch.Tensor:
+    n = int(lib.irbpp_streams_backward_workspace(w.embed, w.hidden, w.atoms, S, B))
+    if n <= 0:
+        raise ValueError("streams_logits_grad: 1 <= embed, hidden <= 256, 2 <= atoms <= 128, 1 <= S <= 1024 and 1 <= B <= 1024")
+    return torch.empty((n // 4,), dtype=torch.float32, device=dev)
+
+
+class _StreamsLogitsGrad(torch.autograd.Function):
+    """streams_logits over the four layers' live parameters with the defined backward: the numpy definition on CPU tensors,
+    irbpp_streams_act(_mfma) and irbpp_streams_backward on a HIP device.  The sixteen parameters follow x and xg, layer by
+    layer (fc_h_v, fc_z_v, fc_h_a, fc_z_a), each as weight_mu, weight_sigma, bias_mu, bias_sigma."""
+
+    @staticmethod
+    def forward(ctx, x, xg, *rest):
+        weights, lib, form = rest[16:]
+        ctx.weights, ctx.lib = weights, lib
+        if lib is None:
+            v, a = _streams_logits_cpu(x, xg, weights)
+        else:
+            _, v, a = _streams_call(lib, x, xg, weights, None, None, None, False, True, form)
+        ctx.save_for_backward(x, xg)
+        return v, a
+
+    @staticmethod
+    def backward(ctx, gv, ga):
+        x, xg = ctx.saved_tensors
+        w, lib = ctx.weights, ctx.lib
+        B, S, _ = x.shape
+        need = ctx.needs_input_grad
+        names = [f"{layer}_{p}" for layer in ("hv", "zv", "ha", "za") for p in _NOISY_PARAMS]
+        eps = w.eps                                          # as the forward met it; None in eval mode
+        eff = (w.w_hv, w.b_hv, w.w_zv, w.b_zv, w.w_ha, w.b_ha, w.w_za, w.b_za)
+        if lib is None:
+            import numpy as np
+            n = lambda t: None if t is None else t.detach().to(torch.float32).contiguous().numpy()    # noqa: E731
+            dx, dxg, grads = _streams_grad_backward_np(n(x), n(xg), [n(t) for t in eff], None if eps is None else [n(t) for t in eps],
+                                                       n(ga), n(gv))
+            t = lambda arr: None if arr is None else torch.from_numpy(np.ascontiguousarray(arr))       # noqa: E731
+            out = [t(dx) if need[0] else None, t(dxg) if need[1] else None]
+            out += [t(grads[nm]) if need[2 + i] else None for i, nm in enumerate(names)]
+            return tuple(out) + (None, None, None)
+        from . import _lib
+        dev = x.device
+        gv = None if gv is None else gv.detach().to(torch.float32).contiguous()
+        ga = None if ga is None else ga.detach().to(torch.float32).contiguous()
+        dx = torch.empty((B, S, w.embed), dtype=torch.float32, device=dev) if need[0] else None
+        dxg = torch.empty((B, w.embed), dtype=torch.float32, device=dev) if need[1] else None
+        shapes = {"weight": {"hv": (w.hidden, w.embed), "zv": (w.atoms, w.hidden), "ha": (w.hidden, w.embed), "za": (w.atoms, w.hidden)},
+                  "bias": {"hv": (w.hidden,), "zv": (w.atoms,), "ha": (w.hidden,), "za": (w.atoms,)}}
+        outs = []
+        for i, nm in enumerate(names):
+            layer, kind, which = nm.split("_")
+            want = need[2 + i] and (which == "mu" or eps is not None)
+            outs.append(torch.empty(shapes[kind][layer], dtype=torch.float32, device=dev) if want else None)
+        ws = _streams_grad_workspace(lib, w, S, B, dev)
+        noise = _IrbppStreamNoise(*(t.data_ptr() for t in eps)) if eps is not None else None
+        grads = _IrbppStreamGrads(*(0 if t is None else t.data_ptr() for t in outs))
+        wst = w._struct()
+        _lib.check(lib.irbpp_streams_backward(C.byref(wst), C.byref(noise) if noise is not None else None, _p(xg), xg.stride(0), _p(x),
+                                              x.stride(0), x.stride(1), _p(ga), _p(gv), S, B, _p(ws), _p(dx), _p(dxg), C.byref(grads),
+                                              _stream(dev)), "irbpp_streams_backward")
+        return (dx, dxg) + tuple(outs) + (None, None, None)
+
+
+def streams_logits_grad(x: torch.Tensor, x_global: torch.Tensor, fc_h_v, fc_z_v, fc_h_a, fc_z_a, *,
+                        training: Optional[bool] = None, use_hip: Optional[bool] = None,
+                        form: str = "chain") -> Tuple[torch.Tensor, torch.Tensor]:
+    """The value and advantage streams in the forward that carries a gradient (Agent.learn's online forward, model.py:393-394)
+    over the four NoisyLinear layers' live parameters -> (v float32 [B, atoms], a float32 [B, S, atoms]) with a ``grad_fn``:
+    the logits ``DQNBPP.forward`` combines, in place of ``fc_z_v(relu(fc_h_v(xGlobal)))`` and ``fc_z_a(relu(fc_h_a(x)))``.
+    ``training=None`` follows ``fc_h_v.training`` where the layer has one, else True: the effective weights are
+    ``mu + sigma * epsilon`` in training mode and ``mu`` in eval mode, in which the sigmas get no gradient.  Nothing is kept
+    between calls: every call reads the parameters and the noise as they are.
+
+    Forms: on CPU tensors the numpy emulation of the definition, the forward's (streams_logits') and the backward's
+    (csrc/irbpp_streams_grad.hip); on a HIP device with ``use_hip=True`` (``None`` takes STREAMS_GRAD_HIP_DEFAULT) the forward
+    is irbpp_noisy_weights and irbpp_streams_act (``form="mfma"``: irbpp_streams_act_mfma, the same bits) and the backward
+    irbpp_streams_backward: ordered fmaf chains without atomics, so x's, x_global's and the sixteen parameters' gradients are
+    the same bits on every run and equal to the CPU form's; else torch's ``F.linear`` / ``relu`` on ``mu + sigma * epsilon``
+    under ordinary autograd.  The kernels take 1 <= B <= 1024 besides streams_logits' limits (ValueError otherwise); a
+    detached ``x`` skips its gradient's launch work."""
+    if training is None:
+        training = bool(getattr(fc_h_v, "training", True))
+    layers = (fc_h_v, fc_z_v, fc_h_a, fc_z_a)
+    lib = _head_lib(x, use_hip, STREAMS_GRAD_HIP_DEFAULT)
+    if lib is None and x.is_cuda:
+        F = torch.nn.functional
+        eff = [(l.weight_mu + l.weight_sigma * l.weight_epsilon, l.bias_mu + l.bias_sigma * l.bias_epsilon) if training else
+               (l.weight_mu, l.bias_mu) for l in layers]
+        if x_global.dim() == 3 and x_global.shape[1] == 1:
+            x_global = x_global[:, 0]
+        return (F.linear(F.relu(F.linear(x_global, *eff[0])), *eff[1]), F.linear(F.relu(F.linear(x, *eff[2])), *eff[3]))
+    weights = StreamWeights(*layers, training=training)
+    if weights.device != x.device:
+        raise ValueError("streams_logits_grad: the layers and x live on different devices")
+    xs, xg = _streams_inputs(x, x_global, weights)
+    if xs.shape[0] > STREAMS_GRAD_MAX_BATCH:
+        raise ValueError("streams_logits_grad: 1 <= B <= 1024")
+    if lib is not None:
+        form = _streams_form(form, weights)
+    weights.eps = None
+    if training:                                             # the buffers themselves where they are float32: not to be redrawn before backward
+        weights.eps = [_f32(getattr(layer, n).detach(), x.device) for layer in layers for n in ("weight_epsilon", "bias_epsilon")]
+    params = [getattr(layer, n) for layer in layers for n in _NOISY_PARAMS]
+    return _StreamsLogitsGrad.apply(xs, xg, *params, weights, lib, form)
+
+
 # The same question for the shape branch in front of the network (DESIGN.md section 3, "The shape branch"): the
 # de-duplicated torch formulation or the two launches of irbpp_shape_features.  The kernels: tools/shape_feature_rates.py
 # measured them on an MI355X at 0.073 ms against 0.446 ms for torch's layers on the unique ids at 4096 rows of 8 shapes, 0.189
