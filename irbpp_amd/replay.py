@@ -46,6 +46,22 @@ def _stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _pinned(*tensors) -> list:
+    """[(tensor, its version counter now)]: what a hand-written backward will read, or what its caller handed over, beyond the
+    reach of ``ctx.save_for_backward`` (a tensor held by a plain object, or the caller's own tensor where the forward went on
+    with a converted copy).  A detached alias or a view shares its base's counter."""
+    return [(t, t._version) for t in tensors if t is not None]
+
+
+def _check_pinned(pinned: list, what: str) -> None:
+    """autograd's own complaint for a _pinned tensor that was written in place since: the top of every such backward."""
+    for t, version in pinned:
+        if t._version != version:
+            raise RuntimeError(f"{what}: one of the variables needed for gradient computation has been modified by an inplace "
+                               f"operation: a {t.dtype} tensor of shape {list(t.shape)} is at version {t._version}; expected "
+                               f"version {version} instead")
+
+
 class VectorReplayMemory(object):
     def __init__(self, num_envs: int, capacity: int, obs_len: int, *, discount: float = 0.99, multi_step: int = 3,
                  priority_weight: float = 0.4, priority_exponent: float = 0.5, device="cpu",
@@ -766,7 +782,7 @@ class _DuelingLossFunction(torch.autograd.Function):
     _dueling_v / _c51_block leave them, actions int64 [B] and m float32 [B, atoms] contiguous, all on one HIP device."""
 
     @staticmethod
-    def forward(ctx, v, a, actions, m):
+    def forward(ctx, v, a, actions, m, pinned):
         from . import _lib
         lib = _lib.load()
         B, S, atoms = a.shape
@@ -774,8 +790,8 @@ class _DuelingLossFunction(torch.autograd.Function):
         g = torch.empty((B, atoms), dtype=torch.float32, device=a.device)
         _lib.check(lib.irbpp_dueling_loss(_p(v), v.stride(0), _p(a), a.stride(0), a.stride(1), _p(actions), _p(m), atoms, S, B,
                                           _p(loss), _p(g), _stream(a.device)), "irbpp_dueling_loss")
-        ctx.save_for_backward(g, actions)
-        ctx.rows = S
+        ctx.save_for_backward(g, actions, v, a, m)            # v, a and m only for their version check: g holds what they gave
+        ctx.rows, ctx.pinned = S, pinned
         return loss
 
     @staticmethod
@@ -783,17 +799,18 @@ class _DuelingLossFunction(torch.autograd.Function):
     def backward(ctx, grad_loss):
         need_v, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (need_v or need_a):
-            return None, None, None, None
+            return None, None, None, None, None
         from . import _lib
         lib = _lib.load()
-        g, actions = ctx.saved_tensors
+        g, actions = ctx.saved_tensors[:2]                    # raises if one of the five was written in place since the forward
+        _check_pinned(ctx.pinned, "dueling_c51_loss")
         B, atoms = g.shape
         grad_loss = grad_loss.to(torch.float32).contiguous()      # loss.sum().backward() hands over a stride-0 expanded tensor
         grad_v = torch.empty((B, atoms), dtype=torch.float32, device=g.device) if need_v else None
         grad_a = torch.empty((B, ctx.rows, atoms), dtype=torch.float32, device=g.device) if need_a else None
         _lib.check(lib.irbpp_dueling_loss_backward(_p(g), _p(grad_loss), _p(actions), atoms, ctx.rows, B, _p(grad_v), _p(grad_a),
                                                    _stream(g.device)), "irbpp_dueling_loss_backward")
-        return grad_v, grad_a, None, None
+        return grad_v, grad_a, None, None, None
 
 
 def dueling_c51_loss(v: torch.Tensor, a: torch.Tensor, actions: torch.Tensor, m: torch.Tensor, *,
@@ -805,8 +822,10 @@ def dueling_c51_loss(v: torch.Tensor, a: torch.Tensor, actions: torch.Tensor, m:
     ``use_hip=True`` (a HIP device; ``None`` takes DUELING_LOSS_HIP_DEFAULT) one kernel computes the loss in a defined float32
     arithmetic (irbpp_dueling_loss: only the action's row and the column means, no [B, S, atoms] log-probabilities) and one
     more writes the gradients (irbpp_dueling_loss_backward, only the sides that require one; ``v.grad`` in the shape ``v``
-    was given in); an action outside [-S, S) then gives a NaN loss and zero gradients.  Otherwise, and on the CPU, the
-    reference's torch lines run under ordinary autograd (and refuse such an action as torch indexing does)."""
+    was given in); an action outside [-S, S) then gives a NaN loss and zero gradients; an in-place write to ``v``, ``a``,
+    ``actions`` or ``m`` before the backward makes it raise autograd's "modified by an inplace operation" RuntimeError.
+    Otherwise, and on the CPU, the reference's torch lines run under ordinary autograd (and refuse such an action as torch
+    indexing does): torch's own graph keeps ``actions`` and ``m`` to that rule and never reads ``v`` or ``a`` again."""
     v, a = _dueling_logits(v, a)
     B, S, atoms = a.shape
     if tuple(actions.shape) != (B,) or actions.dtype.is_floating_point:
@@ -821,7 +840,7 @@ def dueling_c51_loss(v: torch.Tensor, a: torch.Tensor, actions: torch.Tensor, m:
         return -torch.sum(m.to(a.device) * log_ps_a, 1)
     dev = a.device
     return _DuelingLossFunction.apply(_dueling_v(v), _c51_block(a), actions.to(device=dev, dtype=torch.int64).contiguous(),
-                                      _f32(m, dev))
+                                      _f32(m, dev), _pinned(v, a, actions, m))
 
 
 def learn_loss(online_logits, target_logits, batch, support: torch.Tensor, gamma_n: float, v_min: float, v_max: float, *,
@@ -1133,27 +1152,32 @@ def _streams_grad_workspace(lib, w: StreamWeights, S: int, B: int, dev) -> torch
 class _StreamsLogitsGrad(torch.autograd.Function):
     """streams_logits over the four layers' live parameters with the defined backward: the numpy definition on CPU tensors,
     irbpp_streams_act(_mfma) and irbpp_streams_backward on a HIP device.  The sixteen parameters follow x and xg, layer by
-    layer (fc_h_v, fc_z_v, fc_h_a, fc_z_a), each as weight_mu, weight_sigma, bias_mu, bias_sigma."""
+    layer (fc_h_v, fc_z_v, fc_h_a, fc_z_a), each as weight_mu, weight_sigma, bias_mu, bias_sigma; then the eight epsilon buffers,
+    layer by layer as weight_epsilon, bias_epsilon.  All twenty-six are saved for the backward, in either mode, so that autograd
+    refuses a backward after any of them was written in place; ``pinned`` holds the call's own effective weights and the
+    caller's x and x_global to the same rule."""
 
     @staticmethod
     def forward(ctx, x, xg, *rest):
-        weights, lib, form = rest[16:]
-        ctx.weights, ctx.lib = weights, lib
+        weights, lib, form, pinned = rest[24:]
+        ctx.weights, ctx.lib, ctx.pinned = weights, lib, pinned
         if lib is None:
             v, a = _streams_logits_cpu(x, xg, weights)
         else:
             _, v, a = _streams_call(lib, x, xg, weights, None, None, None, False, True, form)
-        ctx.save_for_backward(x, xg)
+        ctx.save_for_backward(x, xg, *rest[:24])
         return v, a
 
     @staticmethod
     def backward(ctx, gv, ga):
-        x, xg = ctx.saved_tensors
+        saved = ctx.saved_tensors                            # raises if one of them was written in place since the forward
+        _check_pinned(ctx.pinned, "streams_logits_grad")
+        x, xg = saved[:2]
         w, lib = ctx.weights, ctx.lib
         B, S, _ = x.shape
         need = ctx.needs_input_grad
         names = [f"{layer}_{p}" for layer in ("hv", "zv", "ha", "za") for p in _NOISY_PARAMS]
-        eps = w.eps                                          # as the forward met it; None in eval mode
+        eps = [_f32(t.detach(), x.device) for t in saved[18:]] if w.training else None      # unchanged since the forward
         eff = (w.w_hv, w.b_hv, w.w_zv, w.b_zv, w.w_ha, w.b_ha, w.w_za, w.b_za)
         if lib is None:
             import numpy as np
@@ -1163,7 +1187,7 @@ class _StreamsLogitsGrad(torch.autograd.Function):
             t = lambda arr: None if arr is None else torch.from_numpy(np.ascontiguousarray(arr))       # noqa: E731
             out = [t(dx) if need[0] else None, t(dxg) if need[1] else None]
             out += [t(grads[nm]) if need[2 + i] else None for i, nm in enumerate(names)]
-            return tuple(out) + (None, None, None)
+            return tuple(out) + (None,) * 12
         from . import _lib
         dev = x.device
         gv = None if gv is None else gv.detach().to(torch.float32).contiguous()
@@ -1184,7 +1208,7 @@ class _StreamsLogitsGrad(torch.autograd.Function):
         _lib.check(lib.irbpp_streams_backward(C.byref(wst), C.byref(noise) if noise is not None else None, _p(xg), xg.stride(0), _p(x),
                                               x.stride(0), x.stride(1), _p(ga), _p(gv), S, B, _p(ws), _p(dx), _p(dxg), C.byref(grads),
                                               _stream(dev)), "irbpp_streams_backward")
-        return (dx, dxg) + tuple(outs) + (None, None, None)
+        return (dx, dxg) + tuple(outs) + (None,) * 12
 
 
 def streams_logits_grad(x: torch.Tensor, x_global: torch.Tensor, fc_h_v, fc_z_v, fc_h_a, fc_z_a, *,
@@ -1195,7 +1219,10 @@ def streams_logits_grad(x: torch.Tensor, x_global: torch.Tensor, fc_h_v, fc_z_v,
     the logits ``DQNBPP.forward`` combines, in place of ``fc_z_v(relu(fc_h_v(xGlobal)))`` and ``fc_z_a(relu(fc_h_a(x)))``.
     ``training=None`` follows ``fc_h_v.training`` where the layer has one, else True: the effective weights are
     ``mu + sigma * epsilon`` in training mode and ``mu`` in eval mode, in which the sigmas get no gradient.  Nothing is kept
-    between calls: every call reads the parameters and the noise as they are.
+    between calls: every call reads the parameters and the noise as they are, into effective weights of its own.  Until its
+    backward has run, x, x_global, the sixteen parameters and the eight epsilon buffers must stay as they are: an in-place
+    write to any of them (``reset_noise()``, an optimiser step, a copy from another network) makes the backward raise
+    autograd's "modified by an inplace operation" RuntimeError, in either mode, instead of returning another gradient.
 
     Forms: on CPU tensors the numpy emulation of the definition, the forward's (streams_logits') and the backward's
     (csrc/irbpp_streams_grad.hip); on a HIP device with ``use_hip=True`` (``None`` takes STREAMS_GRAD_HIP_DEFAULT) the forward
@@ -1223,11 +1250,15 @@ def streams_logits_grad(x: torch.Tensor, x_global: torch.Tensor, fc_h_v, fc_z_v,
         raise ValueError("streams_logits_grad: 1 <= B <= 1024")
     if lib is not None:
         form = _streams_form(form, weights)
-    weights.eps = None
-    if training:                                             # the buffers themselves where they are float32: not to be redrawn before backward
-        weights.eps = [_f32(getattr(layer, n).detach(), x.device) for layer in layers for n in ("weight_epsilon", "bias_epsilon")]
+    # The backward reads x, x_global and the epsilon buffers where they lie (no copy is taken) and this call's own effective
+    # weights (``weights``: built above, private to the call, so a later forward cannot overwrite them).  Everything the caller
+    # handed over goes to save_for_backward, and ``pinned`` covers what that cannot reach: a reset_noise(), an optimiser step
+    # or a target copy into any of them before the backward raises there instead of changing the gradient.
     params = [getattr(layer, n) for layer in layers for n in _NOISY_PARAMS]
-    return _StreamsLogitsGrad.apply(xs, xg, *params, weights, lib, form)
+    noise = [getattr(layer, n) for layer in layers for n in ("weight_epsilon", "bias_epsilon")]
+    w = weights
+    pinned = _pinned(x, x_global, w.w_hv, w.b_hv, w.w_zv, w.b_zv, w.w_ha, w.b_ha, w.w_za, w.b_za)
+    return _StreamsLogitsGrad.apply(xs, xg, *params, *noise, weights, lib, form, pinned)
 
 
 # The same question for the shape branch in front of the network ("The shape branch"): the
@@ -1255,6 +1286,8 @@ class ShapePoints(object):
         if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
             raise ValueError("shape_array must be [n_shapes, P, 3]")
         self.points = t.detach().to(device=device, dtype=torch.float32).contiguous()
+        if self.points.data_ptr() == t.data_ptr():           # a float32 array on the CPU: a table of its own, once, since a write
+            self.points = self.points.clone()                # to the caller's array would pass every version check
         self.device = self.points.device
         self.n_shapes, self.n_points = int(t.shape[0]), int(t.shape[1])
         self._workspace = {}
@@ -1507,10 +1540,10 @@ class _ShapeFeaturesGrad(torch.autograd.Function):
     CPU tensors, irbpp_shape_features_arg / irbpp_shape_features_backward on a HIP device."""
 
     @staticmethod
-    def forward(ctx, w1, b1, w2, b2, ids, indices, points, slope, lib):
+    def forward(ctx, w1, b1, w2, b2, ids, indices, points, slope, lib, pinned):
         dev = points.device
         M, k, H1, F_ = int(ids.shape[0]), int(indices.shape[0]), int(w1.shape[0]), int(w2.shape[0])
-        ctx.points, ctx.slope, ctx.lib = points, slope, lib
+        ctx.points, ctx.slope, ctx.lib, ctx.pinned = points, slope, lib, pinned
         if lib is None:
             import numpy as np
             n = lambda t: t.detach().cpu().numpy()           # noqa: E731
@@ -1528,19 +1561,20 @@ class _ShapeFeaturesGrad(torch.autograd.Function):
                                                     1 if ids.is_floating_point() else 0, max(int(ids.stride(0)), 1), M, C.byref(enc),
                                                     _p(key_ws), _p(j_ws), chunks, _p(out), F_, _p(arg), _stream(dev)),
                        "irbpp_shape_features_arg")
-        ctx.save_for_backward(w1, b1, w2, b2, ids, indices, arg)
+        ctx.save_for_backward(w1, b1, w2, b2, ids, indices, arg, points.points)     # the table as this forward read it
         ctx.mark_non_differentiable(arg)
         return out, arg
 
     @staticmethod
     def backward(ctx, grad_out, _grad_arg):
-        w1, b1, w2, b2, ids, indices, arg = ctx.saved_tensors
+        w1, b1, w2, b2, ids, indices, arg, table = ctx.saved_tensors     # raises if one was written in place since the forward
+        _check_pinned(ctx.pinned, "shape_features_grad")       # the caller's own tensors, where the ones above are converted copies
         points, slope, lib = ctx.points, ctx.slope, ctx.lib
         g = grad_out.detach().to(torch.float32).contiguous()
         if lib is None:
             import numpy as np
             n = lambda t: t.detach().cpu().numpy()           # noqa: E731
-            grads = _shape_grad_backward_np(n(points.points), n(indices).astype(np.int64), _shape_ids(ids, points.n_shapes).numpy(),
+            grads = _shape_grad_backward_np(n(table), n(indices).astype(np.int64), _shape_ids(ids, points.n_shapes).numpy(),
                                             n(w1), n(b1), n(w2), n(b2), slope, n(arg), n(g))
             grads = tuple(torch.from_numpy(np.ascontiguousarray(t)) for t in grads)
         else:
@@ -1550,12 +1584,12 @@ class _ShapeFeaturesGrad(torch.autograd.Function):
             grads = tuple(torch.empty_like(t) for t in (w1, b1, w2, b2))
             pd_ws, first_ws = points._grad_workspace(H1, F_)
             enc = _IrbppShapeEncoder(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), H1, F_, slope)
-            _lib.check(lib.irbpp_shape_features_backward(_p(points.points), points.n_shapes, points.n_points, _p(indices),
+            _lib.check(lib.irbpp_shape_features_backward(_p(table), points.n_shapes, points.n_points, _p(indices),
                                                          int(indices.shape[0]), _p(ids), 1 if ids.is_floating_point() else 0,
                                                          max(int(ids.stride(0)), 1), int(ids.shape[0]), C.byref(enc), _p(arg), _p(g),
                                                          _p(pd_ws), _p(first_ws), *(_p(t) for t in grads), _stream(dev)),
                        "irbpp_shape_features_backward")
-        return grads + (None,) * 5
+        return grads + (None,) * 6
 
 
 def _shape_features_grad_torch(ids, points: ShapePoints, indices, w1, b1, w2, b2, slope: float) -> torch.Tensor:
@@ -1583,7 +1617,9 @@ def shape_features_grad(ids: torch.Tensor, points: ShapePoints, indices: torch.T
     HIP device with ``use_hip=True`` (``None`` takes SHAPE_GRAD_HIP_DEFAULT) irbpp_shape_features_arg and, in the backward,
     irbpp_shape_features_backward: the forward's bits are shape_features', the four gradients are reproducible bit for bit
     (ordered chains, no atomics) and equal to the CPU form's; else torch's layers on the unique ids with torch's autograd.
-    The points and the ids carry no gradient.  ``return_arg=True`` returns ``(shape_feature, arg)``, arg int32 [n_shapes, F]:
+    The points and the ids carry no gradient.  The backward reads the four parameters, ``ids``, ``indices`` and the points'
+    table where they lie: an in-place write to any of them before it makes it raise autograd's "modified by an inplace
+    operation" RuntimeError.  ``return_arg=True`` returns ``(shape_feature, arg)``, arg int32 [n_shapes, F]:
     the position in ``indices`` of each feature's maximum per shape that occurs (the smallest one among ties), -1 elsewhere;
     the torch form keeps no such record and raises."""
     dev = points.device
@@ -1596,6 +1632,7 @@ def shape_features_grad(ids: torch.Tensor, points: ShapePoints, indices: torch.T
         raise ValueError("shape encoder: 1 <= H1, F <= 256 and negative_slope >= 0")
     if any(t.device != dev for t in (w1, b1, w2, b2)):
         raise ValueError("shape_features_grad: the layers and the points live on different devices")
+    given_ids, given_indices = ids, indices
     ids = ids.detach()
     if ids.device != dev:
         ids = ids.to(dev)
@@ -1616,7 +1653,7 @@ def shape_features_grad(ids: torch.Tensor, points: ShapePoints, indices: torch.T
     if lib is not None and M > 1 and ids.stride(0) < 1:
         ids = ids.contiguous()
     live = tuple(t.to(torch.float32).contiguous() for t in (w1, b1, w2, b2))     # the parameters themselves where they are both
-    out, arg = _ShapeFeaturesGrad.apply(*live, ids, indices, points, slope, lib)
+    out, arg = _ShapeFeaturesGrad.apply(*live, ids, indices, points, slope, lib, _pinned(w1, b1, w2, b2, given_ids, given_indices))
     return (out, arg) if return_arg else out
 
 
