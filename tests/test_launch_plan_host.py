@@ -166,6 +166,43 @@ ROWS = [
     # a launch over some of the bins (a listed reset) goes by ITS size
     row("s1", 8192, [env("_s1", 2047, 0), trace("", 2047, 0), poly(4094, 0), emit("_s1", 2047, 0)], mode=RESET, n=2047, listed=1),
     row("s1", 8192, [env("_s1", 1024, 0), trace("_c32", 2048, 0), poly(2048, 0), emit("_s1", 1024, 0)], mode=RESET, n=1024, listed=1),
+    # registered observation buffers (tests/test_gpu_registered_obs.py plays these): a launch that observes all bins tracks the
+    # row counts whatever the key, the form of the emit stage or the tuning; one that writes another layout through the
+    # pointer (a listed reset, a buffered step / reset) forgets them
+    row("s1", 1024, [apply("_cells", 256), env("_s1", 1024, 4), trace("_c32", 2048, 1), poly(2048, 1), emit("_s1", 1024, 1)],
+        {"obs_rows": TRACK}, key=CELLS, reg=1),
+    row("s1", 1024, [apply("_heur", 256), env("_s1", 1024, 4), trace("_c32", 2048, 1), poly(2048, 1), emit("_s1", 1024, 1)],
+        {"obs_rows": TRACK}, key=HEUR, reg=1),
+    row("s1", 1024, ["irbpp_heuristic_kernel 1024 256 {full} 1", apply("_cells", 256), env("_s1", 1024, 4), trace("_c32", 2048, 1),
+                     poly(2048, 1), emit("_s1", 1024, 1)], {"obs_rows": TRACK}, key=HEUR_HM, reg=1),
+    row("s1", 1024, [apply("_cells_wg", 1024)], {"obs_rows": FORGET}, K=10, key=CELLS, reg=1),
+    row("s1", 2048, [apply("_heur", 512)], {"obs_rows": FORGET}, K=10, key=HEUR, reg=1),
+    row("s1", 1024, [f"irbpp_env_kernel_chain_s1 1024 256 {15328 + CHAIN_EXTRA} 1"], {"obs_rows": TRACK}, tuning=T.TUNE_CHAIN, reg=1),
+    row("s1", 1024, [f"irbpp_env_kernel_chain_s1 1024 256 {15328 + CHAIN_EXTRA} 0"], {"obs_rows": TRACK}, tuning=T.TUNE_CHAIN, mode=RESET, reg=1),
+    row("s1", 1024, [f"irbpp_env_kernel_chain_s1 1024 256 {15328 + CHAIN_EXTRA} 2"], {"obs_rows": TRACK}, K=10, tuning=T.TUNE_CHAIN, mode=CANDS, reg=1),
+    row("s1", 1024, [apply("_wg", 1024)], {"obs_rows": FORGET}, K=10, tuning=T.TUNE_CHAIN, reg=1),
+    row("s1", 64, [env("_s1", 64, 1), trace("_c32", 128, 1), poly(128, 1), emit("_s1", 64, 1)], {"obs_rows": TRACK}, tuning=T.TUNE_GRAPH, reg=1),
+    row("s1", 64, [env("_s1", 64, 1), trace("_c32", 128, 1), poly(128, 1), emit("_wave_s1", 16, 1)], {"obs_rows": TRACK},
+        tuning=T.TUNE_GRAPH | T.TUNE_WAVE_EMIT, reg=1),
+    row("s1", 67, [env("_s1", 67, 1), trace("_c32", 134, 1), poly(134, 1), emit("_wave_s1", 17, 1)], {"obs_rows": TRACK}, tuning=T.TUNE_WAVE_EMIT, reg=1),
+    row("s1", 67, [env("_s1", 67, 0), trace("_c32", 134, 0), poly(134, 0), emit("_wave_s1", 17, 0)], {"obs_rows": TRACK},
+        tuning=T.TUNE_WAVE_EMIT, mode=RESET, reg=1),
+    row("s1", 35, [env("_s1", 35, 2), trace("_c32", 70, 2), poly(70, 2), emit("_wave_s1", 9, 2)], {"obs_rows": TRACK}, K=10,
+        tuning=T.TUNE_WAVE_EMIT, mode=CANDS, reg=1),
+    # ... a listed reset (a row per LISTED bin), then the step into the same buffer
+    row("s1", 67, [env("_s1", 22, 0), trace("_c32", 44, 0), poly(44, 0), emit("_wave_s1", 6, 0)], {"obs_rows": FORGET},
+        tuning=T.TUNE_WAVE_EMIT, mode=RESET, n=22, listed=1, reg=1),
+    row("s1", 67, [env("_s1", 22, 0), trace("_c32", 44, 0), poly(44, 0), emit("_s1", 22, 0)], {"obs_rows": FORGET},
+        tuning=T.TUNE_BLOCK_EMIT, mode=RESET, n=22, listed=1, reg=1),
+    row("s1", 67, [env("_s1", 67, 1), trace("_c32", 134, 1), poly(134, 1), emit("_s1", 67, 1)], {"obs_rows": TRACK}, tuning=T.TUNE_BLOCK_EMIT, reg=1),
+    # ... the capacity path, online and buffered (K > 1)
+    row("wide20", 96, [apply("_heur", 24), "irbpp_wide_kernel 96 256 -1 4"], {"obs_rows": TRACK}, key=HEUR, reg=1),
+    row("wide20", 96, ["irbpp_wide_kernel 96 256 -1 0"], {"obs_rows": TRACK}, mode=RESET, reg=1),
+    row("wide20", 96, ["irbpp_wide_kernel 30 256 -1 0"], {"obs_rows": FORGET}, mode=RESET, n=30, listed=1, reg=1),
+    row("wide20", 96, ["irbpp_wide_kernel 96 256 -1 2"], {"obs_rows": TRACK}, K=3, mode=CANDS, reg=1),
+    row("wide20", 96, ["irbpp_wide_kernel 96 256 -1 0"], {"obs_rows": FORGET}, K=3, mode=RESET, reg=1),
+    row("wide20", 96, [apply("_cells_wg", 96)], {"obs_rows": FORGET}, K=3, key=CELLS, reg=1),
+    row("wide20", 2048, [apply("", 512)], {"obs_rows": FORGET}, K=3, reg=1),
 ]
 
 
